@@ -15,6 +15,14 @@ resident batch (--max-batch-frames, 80 GiB) runs it as sub-batches, each
 generated on device untimed and timed like one batch; the step time is the
 sum over sub-batches.
 
+A plain run (no --full) does what the headline needs and nothing else: it
+generates the batch, picks the schedule, warms up, times --steps steps,
+writes --dump-outputs if asked and prints the line.  --full adds every other
+leg to the same line as before: the host-resident leg (e2e_host), the cfg5
+same-job anchor (cfg5_job), the plain-allocation rate beside a probed
+placement, the byte-for-byte verification on the device and the CPU
+baseline; --config cfg1 and --config e2e (other workloads) need --full too.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the formulas.
 """
 from __future__ import annotations
@@ -50,6 +58,17 @@ def parse():
     p.add_argument("--e2e-gib", type=float, default=4.0,
                    help="host-resident end-to-end shard per rank in GiB: the e2e_host key of a cfg2 run "
                         "(0 = skip), or the workload of --config e2e")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline: e2e_host (--e2e-gib), cfg5_job (--cfg5-anchor), "
+                        "the plain-allocation rate of --placement probe, the device byte check (unless "
+                        "--no-verify) and cpu_baseline (--cpu-seconds); required by --config cfg1 and e2e. "
+                        "Without it those keys of the line are null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step left to DIR/<name>.npy (rank r > 0: "
+                        "<name>_rank<r>.npy): payload_sample (float32, the batch's bytes at sorted positions "
+                        "drawn from --seed, the whole batch if it is small), payload_head and payload_tail "
+                        "(float32, first and last frame), frame_byte_sums (float64, the byte sum of each of the "
+                        "first 2 Mi frames) and status (float64, the workspace status word); under 64 MB in all")
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--frames", type=int, default=1 << 20, help="frames per GPU")
@@ -77,7 +96,16 @@ def parse():
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="harness collectives (barrier, max time); nccl = RCCL. gloo lets several ranks share one "
                         "GPU to rehearse the N>1 path")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.config != "cfg2" and not a.full:
+        p.error(f"--config {a.config} is not the headline workload: run it with --full")
+    if a.dump_outputs and a.config != "cfg2":
+        p.error("--dump-outputs writes the headline workload's outputs (--config cfg2)")
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # the legs beside the headline are off
+        a.e2e_gib, a.cfg5_anchor, a.cpu_seconds, a.no_verify, a.no_plain = 0.0, 0, 0.0, True, True
+    return a
 
 
 def host_cores():
@@ -692,7 +720,47 @@ def run_e2e(a, kmws, torch, dist, dev, coll_dev, rank, world, ndev, gib=None, st
                             "compare raw_h2d / raw_d2h per rank at N with N = 1"}
 
 
-def run_job(a, kmws, torch, dist, dev, coll_dev, rank, world, job_frames, shared_gpu, with_plain=True):
+DUMP_SAMPLE = 1 << 22  # bytes of the batch sampled into payload_sample.npy (16 MB as float32)
+DUMP_FRAMES = 1 << 21  # frames whose byte sums go into frame_byte_sums.npy (16 MB as float64)
+DUMP_EDGE = 1 << 16    # bytes of the first and of the last frame kept
+
+
+def dump_outputs(a, torch, base, bn, L, status, rank, world):
+    """--dump-outputs: what the last timed step left in the batch it ran on (the
+    in-place result a caller of kmws_unmask_batch holds after it), as float
+    arrays small enough to keep: the bytes at DUMP_SAMPLE sorted positions
+    drawn from --seed (every byte of a batch no larger than that), the first
+    and the last frame (DUMP_EDGE bytes of each at most), the byte sums of the
+    first DUMP_FRAMES frames (exact in float64) and the workspace status word.
+    With N ranks each writes its own files and a 1/N share of the sample and
+    of the sums, so a run stays under 64 MB.  The same arguments give the same
+    inputs and the same positions, so two builds can be compared array for
+    array."""
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    span = bn * L
+    count = max(1, DUMP_SAMPLE // world)
+    if span <= count:
+        sample = base[:span]
+    else:
+        pos = np.sort(np.random.default_rng(a.seed).integers(0, span, size=count, dtype=np.int64))
+        sample = base[torch.from_numpy(pos).to(base.device)]
+    nsum = min(bn, max(1, DUMP_FRAMES // world))
+    sums = torch.empty(nsum, dtype=torch.float64, device=base.device)
+    rows = max(1, (1 << 30) // L)  # 1 GiB of frames per reduction
+    for lo in range(0, nsum, rows):
+        hi = min(nsum, lo + rows)
+        sums[lo:hi] = base[lo * L:hi * L].view(hi - lo, L).sum(dim=1, dtype=torch.int64).to(torch.float64)
+    edge = min(L, DUMP_EDGE)
+    arrays = {"payload_sample": sample.to(torch.float32), "payload_head": base[:edge].to(torch.float32),
+              "payload_tail": base[span - edge:span].to(torch.float32), "frame_byte_sums": sums,
+              "status": torch.tensor([float(status)], dtype=torch.float64)}
+    sfx = f"_rank{rank}" if rank else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(a.dump_outputs, name + sfx + ".npy"), t.cpu().numpy())
+
+
+def run_job(a, kmws, torch, dist, dev, coll_dev, rank, world, job_frames, shared_gpu, with_plain=True, dump=False):
     """One pass of the device-resident unmask over a job: `job_frames` frames
     split over the ranks (strong scaling, BASELINE configs[4]), or 0 = a.frames
     per rank (weak, configs[1]).  A rank's shard larger than one resident batch
@@ -763,6 +831,8 @@ def run_job(a, kmws, torch, dist, dev, coll_dev, rank, world, job_frames, shared
         done += bn
         ranges.append([b_lo, b_hi])
         st |= ws.status()
+        if dump and bn and not any(hi > lo for lo, hi in batches[j + 1:]):
+            dump_outputs(a, torch, base, bn, L, st, rank, world)  # before the verification's extra pass
         if not a.no_verify and bn:
             if (a.warmup + a.steps) % 2 == 0:  # XOR twice is the identity: bring the batch to the unmasked state
                 kmws.unmask_batch(base, bdescs, ws, bspan)
@@ -861,7 +931,8 @@ def main():
                           steps=min(a.steps, 5), warmup=2)
         except Exception as ex:  # recorded, never masking the headline
             e2e = {"error": repr(ex)}
-    r = run_job(a, kmws, torch, dist, dev, coll_dev, rank, world, job_frames, shared_gpu)
+    r = run_job(a, kmws, torch, dist, dev, coll_dev, rank, world, job_frames, shared_gpu,
+                dump=a.dump_outputs is not None)
     # At N = 1 the headline is cfg2 (weak); the N > 1 lines run BASELINE
     # configs[4]'s fixed job (strong).  So that the 1 -> 8 curve has a same-job
     # anchor, N = 1 also times that job, its 8 resident
@@ -900,6 +971,7 @@ def main():
             "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "strong" if job_frames else "weak", "vs_baseline": None,
+            "full": a.full,
             "dtype": "u8",
             "data": "synthetic (device-generated splitmix64 payload, per-frame random keys)",
             "config": {"workload": ("cfg5: fixed job of %d frames split over the GPUs (per-GPU frame partition), "

@@ -16,10 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cfg1_cpu_baseline_runs_without_gpu():
-    """bench.py --config cfg1 on a host without a GPU: the cpu_baseline leg
+    """bench.py --full --config cfg1 on a host without a GPU: the cpu_baseline leg
     (kuma's decoder restated in oracle/) decodes the whole stream; no product
     numbers are reported (no CPU fallback)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg1", "--steps", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "cfg1", "--steps", "2"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -32,6 +32,31 @@ def test_cfg1_cpu_baseline_runs_without_gpu():
         has_gpu = False
     if not has_gpu:
         assert not any(k.startswith("product") for k in d)
+
+
+def test_plain_run_switches_every_side_leg_off(monkeypatch, capsys):
+    """Without --full only the headline runs: the host-resident leg, the cfg5
+    anchor, the CPU baseline, the byte check and the plain-allocation leg are
+    off whatever their own options say, and the other workloads are refused;
+    --full leaves every option as given."""
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--e2e-gib", "1"])
+    a = bench.parse()
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 2, None)
+    assert (a.e2e_gib, a.cfg5_anchor, a.cpu_seconds, a.no_verify, a.no_plain) == (0, 0, 0, True, True)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "7", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.steps, a.dump_outputs) == (True, 7, "d")
+    assert (a.e2e_gib, a.cfg5_anchor, a.cpu_seconds, a.no_verify, a.no_plain) == (4.0, 1, 10.0, False, False)
+    for argv in (["--config", "cfg1"], ["--config", "e2e"], ["--full", "--config", "e2e", "--dump-outputs", "d"],
+                 ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2
+    assert "--full" in capsys.readouterr().err
 
 
 def test_cfg1_wire_decodes_to_plain_payloads():

@@ -18,10 +18,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*args, timeout=300):
+def run_bench(*args, timeout=300, full=True):
+    """bench.py's one JSON line; --full unless told otherwise: these tests read
+    the legs beside the headline (verify, cfg5_job, plain rate)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True,
-                       timeout=timeout, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(["--full"] if full else []), *args],
+                       capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1, r.stdout[-2000:]  # ONE JSON line, whatever the ranks' libraries print
@@ -56,6 +58,55 @@ def test_bench_one_gpu_small_batch_plain_rate():
     assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["verify"]["byte_mismatches"] == 0
     assert d["config"]["placement"]["kind"] == "plain torch.empty"
     assert d["roofline"]["frac_plain"] == d["roofline"]["frac"] > 0  # the timed batch is the plain allocation
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline and nothing else -- the side
+    legs' keys are null -- and --dump-outputs writes what the last timed step
+    left in the batch: here 96 x 64 KiB frames (6 MiB, above bench.DUMP_SAMPLE,
+    so the sampled path) after 2 + 3 passes, an odd count, so the unmasked
+    payload.  Every array equals the oracle's unmask of the same synthetic
+    input, regenerated here from the seeds bench.py documents."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from kuma_amd import kmws
+    from oracle import oracle as orc
+    n, L, steps, warmup = 96, 65536, 3, 2
+    out = tmp_path / "dump"
+    d = run_bench("--gpus", "1", "--frames", str(n), "--steps", str(steps), "--warmup", str(warmup),
+                  "--dump-outputs", str(out), full=False)
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup
+    assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["config"]["total_frames"] == n
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GiB/s" and d["dtype"] == "u8"
+    assert d["metric"] == bench.METRIC and d["higher_is_better"] is True
+    assert d["cfg5_job"] is None and d["e2e_host"] is None and d["cpu_baseline"] is None
+    assert d["plain_allocation"] is None and d["verify"] == {"status_word": 0, "byte_mismatches": None}
+
+    seed = 0x6B756D61  # bench.py --seed default
+    span = n * L
+    base = torch.empty(span, dtype=torch.uint8, device="cuda")
+    descs = torch.empty((n, 2), dtype=torch.int64, device="cuda")
+    kmws.fill_uniform_descs(descs, L, L, seed ^ 0x5EED)
+    kmws.fill_synthetic(base, seed)
+    torch.cuda.synchronize()
+    want = base.cpu().numpy()
+    hd = descs.cpu().numpy().reshape(-1).view(orc.DESC_DTYPE)
+    assert hd.shape == (n,) and int(hd["off"][5]) == 5 * L and int(hd["len"][5]) == L
+    for _ in range((steps + warmup) % 2):
+        orc.unmask_batch(want, hd)
+
+    got = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+    assert sorted(got) == ["frame_byte_sums", "payload_head", "payload_sample", "payload_tail", "status"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10**6
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    pos = np.sort(np.random.default_rng(seed).integers(0, span, size=bench.DUMP_SAMPLE, dtype=np.int64))
+    assert np.array_equal(got["payload_sample"], want[pos].astype(np.float32))
+    assert np.array_equal(got["payload_head"], want[:L].astype(np.float32))
+    assert np.array_equal(got["payload_tail"], want[-L:].astype(np.float32))
+    assert np.array_equal(got["frame_byte_sums"], want.reshape(n, L).sum(axis=1, dtype=np.int64).astype(np.float64))
+    assert np.array_equal(got["status"], np.zeros(1))
 
 
 CFG5_FRAMES = 10485760  # BASELINE configs[4]: 10 M x 64 KiB = 640 GiB

@@ -26,8 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_bench(*args, timeout=300):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True,
-                       timeout=timeout, cwd=ROOT, env=env)
+    # --full: the host-resident workload and the e2e_host leg are not part of a plain run
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], capture_output=True,
+                       text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1, r.stdout[-2000:]

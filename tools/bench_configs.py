@@ -3,7 +3,7 @@
 end-to-end (host-memory) rate.  One JSON line per config on stdout.
 
   cfg1  1000 x 4 KiB masked TEXT frames, SERVER, fed in 64 KiB reads (runs
-        bench.py --config cfg1: kuma's decoder restated in oracle/ as the CPU
+        bench.py --full --config cfg1: kuma's decoder restated in oracle/ as the CPU
         baseline, the product decoder and the batched send path).
   cfg3  Zipf 128 B-1 MiB, ~8 GiB payload, device-resident: encode (header pack
         + mask) -> unpack headers -> gather + unmask; round trip verified.
@@ -44,7 +44,7 @@ def splitmix_keys(seed, n):
 
 # ------------------------------------------------------------------ cfg1
 def cfg1(reps: int):
-    """BASELINE configs[0]: lives in bench.py (`python bench.py --config cfg1`),
+    """BASELINE configs[0]: lives in bench.py (`python bench.py --full --config cfg1`),
     whose cpu_baseline leg times kuma's decoder restated in oracle/."""
     sys.path.insert(0, ROOT)
     import bench

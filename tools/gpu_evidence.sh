@@ -12,6 +12,6 @@ export TMPDIR=/tmp
 timeout -k 10 400 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 &&
-timeout -k 10 300 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+timeout -k 10 300 python3 bench.py --full >"$OUT/bench.json" 2> "$OUT/bench.err" &&
 timeout -k 10 500 python3 tools/bench_configs.py ${CONFIGS:-cfg1 cfg2b cfg3 cfg4 e2e} --placement plain \
     > "$OUT/configs.jsonl" 2> "$OUT/configs.err"

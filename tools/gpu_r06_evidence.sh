@@ -18,7 +18,7 @@ echo "== interference" && timeout -k 10 180 /tmp/grid_interference 1048576 20 6 
 echo "== interference trace" && timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/interf_trace" -o run -- \
     /tmp/grid_interference 1048576 20 6 16 > "$OUT/interference_prof.json" 2> "$OUT/interference_prof.err" &&
 python3 tools/phase_stats.py "$OUT/interf_trace" unmask_split_kernel 20 6 3 > "$OUT/interference_trace_phases.json" &&
-echo "== e2e N=1" && timeout -k 10 300 python3 bench.py --config e2e --gpus 1 --e2e-gib 8 --steps 10 --warmup 2 > "$OUT/e2e_n1.json" &&
-echo "== e2e N=2 gloo" && timeout -k 10 300 python3 bench.py --config e2e --gpus 2 --dist-backend gloo --e2e-gib 4 --steps 10 --warmup 2 > "$OUT/e2e_n2_gloo.json" &&
-echo "== bench" && timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+echo "== e2e N=1" && timeout -k 10 300 python3 bench.py --full --config e2e --gpus 1 --e2e-gib 8 --steps 10 --warmup 2 > "$OUT/e2e_n1.json" &&
+echo "== e2e N=2 gloo" && timeout -k 10 300 python3 bench.py --full --config e2e --gpus 2 --dist-backend gloo --e2e-gib 4 --steps 10 --warmup 2 > "$OUT/e2e_n2_gloo.json" &&
+echo "== bench" && timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 echo done
