@@ -274,7 +274,7 @@ kmws_status    kmws_tx_batch_attach_ring(kmws_tx_batch* b, uint8_t* ring, size_t
 int kmws_device_count(void);
 
 /* Workspace bytes needed by kmws_unmask_batch for `span` bytes of payload
- * address space (tile map + status word). */
+ * address space (status word + an 8-byte record per 16 KiB tile). */
 size_t kmws_unmask_workspace_size(uint64_t span);
 
 /* Batched in-place unmask (replaces WSHandler::handleDataMask, WSHandler.cpp:
@@ -307,8 +307,13 @@ kmws_status kmws_unmask_apply(uint8_t* base, uint64_t span, const kmws_desc* des
 #define KMWS_SCHED_SPLIT8       3   /* ... over 8 parts */
 #define KMWS_SCHED_XCD_RUNS     4   /* runs of 16 tiles per XCD */
 #define KMWS_SCHED_SPLIT4       5   /* ... over 4 parts (the default from a 16 KiB mean region) */
-/* Store policy of the payload: non-temporal by default (neither bit, or
- * KMWS_SCHED_NT_STORES); KMWS_SCHED_TEMPORAL_STORES keeps the lines in L2
+/* Store policy of the payload: streaming by default (neither bit, or
+ * KMWS_SCHED_NT_STORES): for batches whose mean frame region is 16 KiB or
+ * more, `nt sc1` buffer stores, which do not keep the line in the XCD's L2 --
+ * the fastest of nt / nt sc1 / sc1 / sc0 sc1 on the 64 GiB aligned batch and
+ * on the packed wire; below that, `nt` stores, which cfg3's Zipf wire needs
+ * (profiles/p01_unmask_tilerec_policy_ab.txt).
+ * KMWS_SCHED_TEMPORAL_STORES stores plain and keeps the lines in L2
  * (written back on eviction) -- slower on plain allocations of every layout
  * measured, a candidate the autotune times.  At most one bit. */
 #define KMWS_SCHED_NT_STORES       (1 << 29)

@@ -65,6 +65,100 @@ __device__ __forceinline__ u32x4 word_byte_range(int lo, int hi)
     return u32x4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
 }
 
+// ---- unmask plan records and the block -> tile mapping (kmws_unmask.hip) ----
+//
+// One record per tile, written by the plan kernels and read by the apply with
+// one 8-byte scalar load: the frame whose region holds the tile start, whether
+// that frame's payload covers the whole tile, and if so its key already
+// rotated for the tile's words.  The flag shares the index word (bit 31), which
+// holds for batches of fewer than 2^31 frames; larger batches never set it and
+// keep all 32 bits for the index (every tile then takes the descriptor paths).
+struct alignas(8) TileRec {
+    uint32_t frame;  // frame index; bit 31: covered (batches below kTileRecMaxFlagged frames)
+    uint32_t rkey;   // covered: rot_key(key, off) of that frame
+};
+// A tile's record and the next tile's (the last tile's is the sentinel), as the apply loads them.
+struct alignas(8) TileRecPair {
+    TileRec at, next;
+};
+constexpr uint32_t kTileRecCovered = 0x80000000u;
+constexpr uint32_t kTileRecMaxFlagged = 0x80000000u;  // n below this: bit 31 of `frame` is the flag
+__host__ __device__ __forceinline__ bool tile_rec_covered(TileRec r, uint32_t n)
+{
+    return n < kTileRecMaxFlagged && (r.frame & kTileRecCovered) != 0u;
+}
+__host__ __device__ __forceinline__ uint32_t tile_rec_frame(TileRec r, uint32_t n)
+{
+    return n < kTileRecMaxFlagged ? r.frame & ~kTileRecCovered : r.frame;
+}
+
+// A placement kind as (k, c, w), all powers of two (c may be 0): blocks dealt
+// over k equal parts of the span (c == 0), or the span cut into runs of c
+// tiles dealt round-robin to the k residues of the block index, the residues
+// in w groups that each keep their runs inside their own w-th of the span.
+struct Split {
+    uint32_t k, c, w;
+};
+// The same, prepared on the host for a span of nfull whole tiles so that the
+// kernel maps a block with shifts, masks and one multiply: no division.
+struct TileMapping {
+    uint32_t whole;  // blocks below this are dealt; the rest take tile = block
+    uint32_t part;   // tiles per part (c == 0) or per group window (c > 0)
+    uint32_t lk;     // log2 k
+    uint32_t lc;     // log2 c (c > 0)
+    uint32_t lw;     // log2 w
+    uint32_t runs;   // c > 0
+};
+__host__ __device__ __forceinline__ uint32_t ilog2_pow2(uint32_t x)
+{
+    uint32_t r = 0;
+    while ((1u << r) < x) ++r;
+    return r;
+}
+__host__ __device__ __forceinline__ TileMapping tile_mapping(uint32_t nfull, Split sp)
+{
+    TileMapping m;
+    m.lk = ilog2_pow2(sp.k);
+    m.lw = ilog2_pow2(sp.w);
+    m.runs = sp.c != 0u;
+    if (!m.runs) {
+        m.lc = 0;
+        m.part = nfull >> m.lk;
+        m.whole = m.part << m.lk;
+    } else {
+        m.lc = ilog2_pow2(sp.c);
+        const uint32_t lrun = m.lk - m.lw + m.lc;  // a group's round of runs: (k / w) * c tiles
+        m.part = ((nfull >> m.lw) >> lrun) << lrun;
+        m.whole = m.part << m.lw;
+    }
+    return m;
+}
+__host__ __device__ __forceinline__ uint32_t tile_of_block(uint32_t b, TileMapping m)
+{
+    if (b >= m.whole) return b;  // past the last whole round: the remaining tiles in order
+    const uint32_t x = b & ((1u << m.lk) - 1u), i = b >> m.lk;
+    if (!m.runs) return x * m.part + i;
+    const uint32_t g = x & ((1u << m.lw) - 1u), xi = x >> m.lw;
+    return g * m.part + ((i >> m.lc) << (m.lk - m.lw + m.lc)) + (xi << m.lc) + (i & ((1u << m.lc) - 1u));
+}
+__host__ __device__ __forceinline__ uint32_t tile_of_block(uint32_t b, uint32_t nfull, Split sp)
+{
+    return tile_of_block(b, tile_mapping(nfull, sp));
+}
+// Placement kind (the low byte of a schedule code, include/kmws_gpu.h) -> Split.
+__host__ __device__ __forceinline__ bool split_of(uint32_t kind, Split* sp)
+{
+    switch (kind) {
+    case KMWS_SCHED_GROUPED_RUNS: *sp = {8u, 16u, 2u}; return true;  // 2 groups of 4 XCDs, runs of 16 per half
+    case KMWS_SCHED_IN_ORDER: *sp = {1u, 0u, 1u}; return true;
+    case KMWS_SCHED_SPLIT2: *sp = {2u, 0u, 1u}; return true;
+    case KMWS_SCHED_SPLIT8: *sp = {8u, 0u, 1u}; return true;
+    case KMWS_SCHED_XCD_RUNS: *sp = {8u, 16u, 1u}; return true;
+    case KMWS_SCHED_SPLIT4: *sp = {4u, 0u, 1u}; return true;
+    default: return false;
+    }
+}
+
 inline kmws_status hip_status(hipError_t e)
 {
     return e == hipSuccess ? KMWS_OK : KMWS_ERR_FAILED;

@@ -6,9 +6,11 @@
 // j of a frame is XORed with maskey[j % 4]; key phase restarts per frame.
 //
 // Layout: the payload address space [0, span) of `base` is cut into fixed
-// tiles of kTile bytes.  A prep kernel writes, for every tile, the index of
-// the frame whose region (its offset up to the next frame's offset) contains
-// the tile start, so a tile block finds its frames with one load.  The main
+// tiles of kTile bytes.  A prep kernel writes, for every tile, a record
+// (TileRec, kmws_common.hpp): the index of the frame whose region (its offset
+// up to the next frame's offset) contains the tile start, whether that frame
+// covers the whole tile, and if so its rotated key -- so a tile block finds
+// its frames, and a covered tile its whole mask, with one scalar load.  The main
 // kernel block (256 lanes) issues its 16-byte loads first, then stages the
 // descriptors of the frames overlapping its tile in LDS and builds a per-word
 // mask (a rotated key splatted over the payload bytes of the word; header or
@@ -20,9 +22,21 @@
 
 namespace kmws {
 
-// Payload store of a tile word: non-temporal (streams past the L2; the
-// default) or temporal (the line stays in L2 and is written back on eviction).
-// On plain allocations non-temporal stores ran ahead on every layout -- the
+// Payload store of a tile word: streaming (the default, and what
+// KMWS_SCHED_NT_STORES asks for) or temporal (plain: the line stays in L2 and
+// is written back on eviction).  The streaming store of the capped launches is
+// `nt sc1`: sc1 stores drop the line from the XCD's L2 where plain, sc0 and nt
+// stores keep it, and on the 64 GiB aligned batch `nt sc1` ran 20.57-20.58 ms
+// against 20.65-20.66 for `nt`, with `sc1` and `sc0 sc1` alone behind both
+// (20.81-20.85); every other load policy than `nt` lost or tied (`nt sc1`
+// loads 20.65-20.67, `sc1` and `sc0 sc1` loads 21.95-21.99); the stand-alone
+// probe (tools/policy_probe.hip) ranks the stores the same way.  The packed
+// wire gained too (20.71-20.80 against 21.04-21.14 ms tuned).  Batches of
+// several frames per tile keep `nt`: with `nt sc1` cfg3's Zipf wire lost
+// (2.70-2.72 against 2.655 ms) where 4 KiB fragments gained (5.22-5.25 against
+// 5.27), and a default must not lose on either
+// (profiles/p01_unmask_tilerec_policy_ab.txt).
+// On plain allocations non-temporal stores ran ahead of temporal on every layout -- the
 // aligned arena 0.82 vs 0.76, the packed wire 0.82 vs 0.76, 4 KiB fragments
 // 0.81 vs 0.76, cfg3's Zipf wire 0.81 vs 0.75 of peak
 // (profiles/r03m_unmask_schedule_sweep_plain_nt_fixed.jsonl) -- so temporal
@@ -32,7 +46,15 @@ namespace kmws {
 // The stores are buffer stores through a per-tile resource with the cache
 // policy as an immediate: written as `if (nt) __builtin_nontemporal_store(..)
 // else *p = ..`, the compiler had merged the two and dropped the hint.
-constexpr int kBufNT = 2;  // buffer cache policy: nt (gfx950; == global_store ... nt)
+// Buffer cache-policy immediates (gfx950): bit 0 sc0, bit 1 nt, bit 4 sc1.
+constexpr int kPolPlain = 0, kPolNT = 2, kPolNTSC1 = 18;
+// What KMWS_SCHED_NT_STORES and the default policy emit: `nt sc1` in the capped
+// launches (mean region of a tile or more: nearly every line is written whole),
+// `nt` in the others (several frames per tile: words of headers and gaps are
+// skipped, lines are written in part).
+constexpr int kPolStreamStoreLarge = kPolNTSC1;
+constexpr int kPolStreamStoreSmall = kPolNT;
+constexpr int kPolStreamLoad = kPolNT;  // every payload load
 constexpr int kBufferRsrcWord3 = 0x00020000;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(uint8_t* base, uint64_t lo, uint64_t hi)
@@ -40,11 +62,43 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(uint8_t* base, uint6
     return __builtin_amdgcn_make_buffer_rsrc(base + lo, (short)0, (int)((hi - lo + 15) & ~15ull), kBufferRsrcWord3);
 }
 
-template <bool NT>
+template <int POL>
 __device__ __forceinline__ void store_word(const u32x4& val, __amdgpu_buffer_rsrc_t rs, uint32_t off)
 {
-    __builtin_amdgcn_raw_buffer_store_b128(val, rs, (int)off, 0, NT ? kBufNT : 0);
+    __builtin_amdgcn_raw_buffer_store_b128(val, rs, (int)off, 0, POL);
 }
+
+// Diagnostic build only (KMWS_DIAG_PHASE_STAMPS, kuma_amd/build.py `defines`;
+// loaded by path by tools/block_phases.py, never the product library): one
+// apply block in 1024 keeps six s_memtime stamps in scalar registers -- entry,
+// index math done, payload loads issued, metadata arrived, first payload word
+// arrived, last store issued -- and writes them to a side buffer at its end.
+// Stamping costs about a tenth of the wave's cycles: the record is for the
+// share of each phase, not for rates.  Without the define no stamp executes.
+#ifdef KMWS_DIAG_PHASE_STAMPS
+constexpr int kDiagStamps = 6;
+constexpr uint32_t kDiagEvery = 1024;
+__device__ uint64_t* g_diag_stamps = nullptr;
+__device__ uint32_t g_diag_slots = 0;
+#define KMWS_STAMP(st, i)                              \
+    do {                                               \
+        __builtin_amdgcn_sched_barrier(0);             \
+        if (st) (st)[i] = __builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_sched_barrier(0);             \
+    } while (0)
+#define KMWS_STAMP_AFTER(st, i, waitcnt)               \
+    do {                                               \
+        __builtin_amdgcn_sched_barrier(0);             \
+        if (st) {                                      \
+            asm volatile("s_waitcnt " waitcnt ::: "memory"); \
+            (st)[i] = __builtin_amdgcn_s_memtime();    \
+        }                                              \
+        __builtin_amdgcn_sched_barrier(0);             \
+    } while (0)
+#else
+#define KMWS_STAMP(st, i) do { (void)(st); } while (0)
+#define KMWS_STAMP_AFTER(st, i, waitcnt) do { (void)(st); } while (0)
+#endif
 
 // Each lane owns V consecutive-block words: word w = tid + kBlock * i.
 template <int V>
@@ -54,12 +108,31 @@ struct UnmaskCfg {
     static constexpr int kCap = kBlock;  // descriptors staged per LDS round
 };
 
+// Frame f's records for the tiles [b0, b1) whose start lies in its region, and
+// the sentinel after the last tile ("next tile's frame" of the last tile).  A
+// tile is covered when the payload [off, off + len) holds all of it -- the
+// test the apply's one-frame path made on the descriptor.
+__device__ __forceinline__ void write_tile_recs(TileRec* __restrict__ map, uint32_t f, uint32_t n, uint64_t off,
+                                                uint32_t len, uint32_t key, uint64_t b0, uint64_t b1,
+                                                uint32_t tile_shift)
+{
+    const uint64_t end = off + len;
+    const uint32_t r = rot_key(key, off);
+    const bool flagged = n < kTileRecMaxFlagged;
+    for (uint64_t b = b0; b < b1; ++b) {
+        const uint64_t lo = b << tile_shift, hi = (b + 1) << tile_shift;
+        const bool cov = flagged && off <= lo && end >= hi;
+        map[b] = TileRec{cov ? f | kTileRecCovered : f, cov ? r : 0u};
+    }
+    if (f == n - 1) map[b1] = TileRec{f, 0u};
+}
+
 // Tile -> first frame map.  Frame f owns tile starts in [start_f, next_f)
 // where start_0 = 0, start_f = off_f, next_f = off_{f+1} (span for the last).
 // Validates sortedness / non-overlap / bounds on the fly.
 __global__ void __launch_bounds__(kBlock) tile_map_kernel(const kmws_desc* __restrict__ d, uint32_t n,
                                                           uint64_t span, uint32_t tile_shift,
-                                                          uint32_t* __restrict__ map,
+                                                          TileRec* __restrict__ map,
                                                           WsHead* __restrict__ head)
 {
     const uint32_t f = blockIdx.x * kBlock + threadIdx.x;
@@ -74,8 +147,7 @@ __global__ void __launch_bounds__(kBlock) tile_map_kernel(const kmws_desc* __res
     const uint64_t T = 1ull << tile_shift;
     const uint64_t b0 = (start + T - 1) >> tile_shift;
     const uint64_t b1 = (next + T - 1) >> tile_shift;
-    for (uint64_t b = b0; b < b1; ++b) map[b] = f;
-    if (f == n - 1) map[b1] = f;  // sentinel after the last tile: "next tile's frame" of the last tile
+    write_tile_recs(map, f, n, df.off, df.len, df.key, b0, b1, tile_shift);
 }
 
 // Descriptor-indexed decode and the unmask plan in one pass
@@ -93,11 +165,11 @@ __global__ void __launch_bounds__(kBlock) unpack_plan_kernel(const uint8_t* __re
                                                              int mode, kmws_desc* __restrict__ out_desc,
                                                              uint16_t* __restrict__ out_flags,
                                                              uint8_t* __restrict__ out_err, uint32_t tile_shift,
-                                                             uint32_t* __restrict__ map, WsHead* __restrict__ head)
+                                                             TileRec* __restrict__ map, WsHead* __restrict__ head)
 {
     const uint32_t f = blockIdx.x * kBlock + threadIdx.x;
     if (f >= n) return;
-    unpack_one(wire, span, hdr_off, n, f, mode, out_desc, out_flags, out_err, head);
+    const kmws_desc df = unpack_one(wire, span, hdr_off, n, f, mode, out_desc, out_flags, out_err, head);
     const uint64_t h = hdr_off[f];
     const uint64_t next = f + 1 < n ? hdr_off[f + 1] : span;
     if (h > next || next > span) {
@@ -108,55 +180,67 @@ __global__ void __launch_bounds__(kBlock) unpack_plan_kernel(const uint8_t* __re
     const uint64_t T = 1ull << tile_shift;
     const uint64_t b0 = (start + T - 1) >> tile_shift;
     const uint64_t b1 = (next + T - 1) >> tile_shift;
-    for (uint64_t b = b0; b < b1; ++b) map[b] = f;
-    if (f == n - 1) map[b1] = f;  // sentinel after the last tile
+    // df: the descriptor this lane just wrote (empty after a header error)
+    write_tile_recs(map, f, n, df.off, df.len, df.key, b0, b1, tile_shift);
 }
 
 // Issue every payload load of a tile.  Full tiles load unconditionally so the
 // loads stay back to back.  Payload is touched once: non-temporal loads and
 // stores (measured +6 % on MI355X for this in-place stream, tools/membw_probe.hip).
-template <int V, bool FULL>
-__device__ __forceinline__ void load_tile(const uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
+// Buffer loads through the tile's resource, the cache policy a template
+// immediate like the stores' (as fast as the global `nt` loads they replaced:
+// 20.65-20.66 ms both, profiles/p01_unmask_tilerec_policy_ab.txt).
+template <int V, bool FULL, int POL = kPolStreamLoad>
+__device__ __forceinline__ void load_tile(uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
                                           u32x4 (&v)[V])
 {
     const int tid = threadIdx.x;
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);  // the stores' resource
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-        if (FULL || a < tile_hi) v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + a));
+        const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
+        if (FULL || tile_lo + x < tile_hi) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)x, 0, POL);
         else v[i] = u32x4{0, 0, 0, 0};
     }
 }
 
-// Mask and store a loaded tile.  f = the tile-map frame, ok = plan status clean.
+// Mask and store a loaded tile.  rec, rec_next = the plan records of the tile
+// and of the one after it, ok = plan status clean; the caller loads all three
+// before the payload, so that they arrive under it.
 template <int V, bool FULL, bool TWO = false, bool NT = true>
 __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
-                                            const kmws_desc* __restrict__ d, uint32_t n,
-                                            const uint32_t* __restrict__ map, uint32_t tile, bool ok,
-                                            const u32x4 (&v)[V], uint64_t* s_off, uint64_t* s_end, uint32_t* s_key,
-                                            const u32x4* pre = nullptr)
+                                            const kmws_desc* __restrict__ d, uint32_t n, TileRec rec,
+                                            TileRec rec_next, bool ok, const u32x4 (&v)[V], uint64_t* s_off,
+                                            uint64_t* s_end, uint32_t* s_key, const u32x4* pre = nullptr,
+                                            uint64_t* stamps = nullptr)
 {
     using Cfg = UnmaskCfg<V>;
+    constexpr int SP = !NT ? kPolPlain : (TWO ? kPolStreamStoreLarge : kPolStreamStoreSmall);  // TWO: the capped launches
     const int tid = threadIdx.x;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);
-    // frames [f, flast] are the only ones that can overlap the tile: flast's
-    // region holds the next tile's start (the map's last entry is a sentinel)
-    uint32_t f = map[tile];
-    const uint32_t flast = map[tile + 1];
+    KMWS_STAMP_AFTER(stamps, 3, "lgkmcnt(0)");  // the records and the status word are here
 
     // Fast path: one frame covers the whole tile (every tile of a 64 KiB-frame
-    // arena).  The test reads block-uniform scalars only, so the branch is
-    // uniform and needs no LDS or barrier.
-    const kmws_desc d0 = d[f < n ? f : 0];
-    if (FULL && f < n && d0.off <= tile_lo && d0.off + d0.len >= tile_hi) {
-        const uint32_t r = rot_key(d0.key, d0.off);
+    // arena).  The plan made the test and rotated the key (write_tile_recs), so
+    // the record is the only metadata the block waits for: no descriptor load
+    // after it.  Block-uniform scalars only: the branch needs no LDS or barrier.
+    if (FULL && tile_rec_covered(rec, n)) {
+        const uint32_t r = rec.rkey;
+        KMWS_STAMP_AFTER(stamps, 4, "vmcnt(3)");  // the first of the V = 4 payload words is here
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-            if (ok) store_word<NT>(v[i] ^ r, rs, (uint32_t)(a - tile_lo));
+            if (ok) store_word<SP>(v[i] ^ r, rs, (uint32_t)(a - tile_lo));
         }
+        KMWS_STAMP(stamps, 5);
         return;
     }
+
+    // frames [f, flast] are the only ones that can overlap the tile: flast's
+    // region holds the next tile's start (the map's last entry is a sentinel)
+    uint32_t f = tile_rec_frame(rec, n);
+    const uint32_t flast = tile_rec_frame(rec_next, n);
+    const kmws_desc d0 = d[f < n ? f : 0];
 
     // Two frames at most (a frame boundary inside the tile, e.g. a packed wire
     // image of frames longer than a tile): both descriptors are block-uniform
@@ -201,7 +285,7 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
         for (int i = 0; i < V; ++i) {
             const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
             if (ok && (m[i].x | m[i].y | m[i].z | m[i].w) != 0u)
-                store_word<NT>(v[i] ^ m[i], rs, (uint32_t)(a - tile_lo));
+                store_word<SP>(v[i] ^ m[i], rs, (uint32_t)(a - tile_lo));
         }
         return;
     }
@@ -268,7 +352,7 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
         const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
         const u32x4 mm = m[i];
         if (ok && (FULL || a < tile_hi) && (mm.x | mm.y | mm.z | mm.w) != 0u)
-            store_word<NT>(v[i] ^ mm, rs, (uint32_t)(a - tile_lo));
+            store_word<SP>(v[i] ^ mm, rs, (uint32_t)(a - tile_lo));
     }
 }
 
@@ -279,7 +363,7 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
 template <int V>
 __global__ void __launch_bounds__(kBlock) unmask_tail_kernel(uint8_t* __restrict__ base, uint64_t span,
                                                              const kmws_desc* __restrict__ d, uint32_t n,
-                                                             const uint32_t* __restrict__ map,
+                                                             const TileRec* __restrict__ map,
                                                              const WsHead* __restrict__ head, uint32_t tile)
 {
     using Cfg = UnmaskCfg<V>;
@@ -290,7 +374,8 @@ __global__ void __launch_bounds__(kBlock) unmask_tail_kernel(uint8_t* __restrict
     u32x4 v[V];
     load_tile<V, false>(base, tile_lo, span, v);
     __builtin_amdgcn_sched_barrier(0);
-    finish_tile<V, false>(base, tile_lo, span, d, n, map, tile, (head->status & kStatusBadDesc) == 0, v, s_off, s_end, s_key);
+    finish_tile<V, false>(base, tile_lo, span, d, n, map[tile], map[tile + 1], (head->status & kStatusBadDesc) == 0,
+                          v, s_off, s_end, s_key);
 }
 
 // One block per full tile, blocks dealt over `k` equal parts of the span:
@@ -303,57 +388,57 @@ __global__ void __launch_bounds__(kBlock) unmask_tail_kernel(uint8_t* __restrict
 template <int V, bool TWO = false, bool NT = true>
 __global__ void __launch_bounds__(kBlock) unmask_split_kernel(uint8_t* __restrict__ base,
                                                               const kmws_desc* __restrict__ d, uint32_t n,
-                                                              const uint32_t* __restrict__ map,
-                                                              const WsHead* __restrict__ head, uint32_t nfull,
-                                                              uint32_t k, uint32_t c, uint32_t b0, uint32_t w)
+                                                              const TileRec* __restrict__ map,
+                                                              const WsHead* __restrict__ head, TileMapping tm,
+                                                              uint32_t b0)
 {
     using Cfg = UnmaskCfg<V>;
     __shared__ uint64_t s_off[Cfg::kCap];
     __shared__ uint64_t s_end[Cfg::kCap];
     __shared__ uint32_t s_key[Cfg::kCap];
-    const uint32_t b = b0 + blockIdx.x;
-    uint32_t tile = b;
-    if (c == 0) {  // k equal parts
-        const uint32_t q = nfull / k;
-        if (b < q * k) tile = (b % k) * q + b / k;
-    } else if (w <= 1) {  // runs of c tiles dealt round-robin over the k residues of b mod k
-        const uint64_t run = (uint64_t)k * c;
-        if (b < nfull / run * run) {
-            const uint32_t x = b % k, i = b / k;
-            tile = (i / c) * (uint32_t)run + x * c + i % c;
-        }
-    } else {  // residues split into w groups, each group's runs inside its own far-apart window
-        const uint32_t kg = k / w;                      // residues per group
-        const uint64_t run = (uint64_t)kg * c;          // tiles per round of a group's runs
-        const uint64_t per = (uint64_t)nfull / w / run * run;
-        if (b < per * w) {
-            const uint32_t x = b % k, i = b / k;
-            const uint32_t g = x % w, xi = x / w;
-            tile = (uint32_t)(g * per) + (i / c) * (uint32_t)run + xi * c + i % c;
-        }
-    }
+#ifdef KMWS_DIAG_PHASE_STAMPS
+    uint64_t st[kDiagStamps] = {};
+#else
+    uint64_t* const st = nullptr;
+#endif
+    KMWS_STAMP(st, 0);
+    const uint32_t tile = tile_of_block(b0 + blockIdx.x, tm);
     const uint64_t lo = (uint64_t)tile * Cfg::kTile;
+    // The tile's two records and the status word go out together, ahead of the
+    // payload loads (scalar loads count on lgkmcnt, the payload on vmcnt: neither
+    // queue holds the other up), and are waited for once, after the payload is
+    // in flight.  A covered tile then needs nothing more before its stores.
+    const TileRecPair recs = *reinterpret_cast<const TileRecPair*>(map + tile);  // one 16-byte scalar load
+    const TileRec rec = recs.at, rec_next = recs.next;
+    const uint32_t status = head->status;
     u32x4 v[V];
     if constexpr (!TWO) {
         // the tile's descriptors first: their wait then counts only them, not the
         // payload loads issued after them (vmcnt is one in-order queue; cfg4's
         // in-place unmask 80.3-80.4 -> 81.7-82.2 %,
         // profiles/r02bt_unmask_desc_prefetch_ab.txt)
-        const uint32_t f = map[tile], fl = map[tile + 1];
+        const uint32_t f = tile_rec_frame(rec, n), fl = tile_rec_frame(rec_next, n);
         const uint32_t fi = f + threadIdx.x;
         u32x4 pre = u32x4{0, 0, 0, 0};
         if (fi < n && fi <= fl) pre = *reinterpret_cast<const u32x4*>(d + fi);
         load_tile<V, true>(base, lo, lo + Cfg::kTile, v);
         __builtin_amdgcn_sched_barrier(0);
-        finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, map, tile, (head->status & kStatusBadDesc) == 0, v, s_off, s_end,
-                                      s_key, &pre);
+        finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next,
+                                      (status & kStatusBadDesc) == 0, v, s_off, s_end, s_key, &pre);
         return;
     }
+    __builtin_amdgcn_sched_barrier(0);
+    KMWS_STAMP(st, 1);
     load_tile<V, true>(base, lo, lo + Cfg::kTile, v);
     __builtin_amdgcn_sched_barrier(0);
-    // the status is read after the payload loads: its latency hides under theirs
-    finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, map, tile, (head->status & kStatusBadDesc) == 0, v, s_off, s_end,
-                                  s_key);
+    KMWS_STAMP(st, 2);
+    finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, (status & kStatusBadDesc) == 0, v,
+                                  s_off, s_end, s_key, nullptr, st);
+#ifdef KMWS_DIAG_PHASE_STAMPS
+    const uint32_t blk = b0 + blockIdx.x;
+    if (blk % kDiagEvery == 0 && blk / kDiagEvery < g_diag_slots && threadIdx.x == 0 && st[5] != 0)
+        for (int i = 0; i < kDiagStamps; ++i) g_diag_stamps[(uint64_t)(blk / kDiagEvery) * kDiagStamps + i] = st[i];
+#endif
 }
 
 // Small host batches: the decoder's payloads of one socket read or one loop
@@ -524,7 +609,7 @@ static kmws_status check_ws(uint64_t span, size_t ws_bytes, uint64_t* ntiles_out
 {
     const uint64_t ntiles = (span + ProdCfg::kTile - 1) / ProdCfg::kTile;
     if (ntiles > 0x7FFFFFFFull) return KMWS_ERR_INVALID_PARAM;
-    if (ws_bytes < sizeof(WsHead) + (ntiles + 1) * sizeof(uint32_t)) return KMWS_ERR_BUFFER_TOO_SMALL;
+    if (ws_bytes < sizeof(WsHead) + (ntiles + 1) * sizeof(TileRec)) return KMWS_ERR_BUFFER_TOO_SMALL;
     *ntiles_out = ntiles;
     return KMWS_OK;
 }
@@ -539,7 +624,7 @@ static kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n
     if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
     if (n == 0 || span == 0) return KMWS_OK;
     hipLaunchKernelGGL(tile_map_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, descs, n, span,
-                       ilog2_u64(ProdCfg::kTile), reinterpret_cast<uint32_t*>(head + 1), head);
+                       ilog2_u64(ProdCfg::kTile), reinterpret_cast<TileRec*>(head + 1), head);
     return hip_status(hipGetLastError());
 }
 
@@ -565,28 +650,14 @@ static kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n
 // (profiles/r03m_unmask_schedule_sweep_plain_nt_fixed.jsonl); non-temporal
 // stores.  The reference's handleDataMask (WSHandler.cpp:303-310) is stateless;
 // so is every batch that was not tuned.
-struct Split {
-    uint32_t k, c, w;
-};
+// The block -> tile mapping of a kind (Split, split_of, tile_of_block) is in
+// kmws_common.hpp: the host prepares it per launch, the kernel applies it.
 constexpr uint32_t kKindMask = 0xFFu;
 constexpr uint32_t kSchedTemporal = KMWS_SCHED_TEMPORAL_STORES;
 constexpr uint32_t kSchedNT = KMWS_SCHED_NT_STORES;
 static uint32_t default_schedule(uint64_t span, uint32_t n)
 {
     return n && span / n >= ProdCfg::kTile ? KMWS_SCHED_SPLIT4 : KMWS_SCHED_GROUPED_RUNS;
-}
-
-static bool split_of(uint32_t kind, Split* sp)
-{
-    switch (kind) {
-    case KMWS_SCHED_GROUPED_RUNS: *sp = {8u, 16u, 2u}; return true;  // 2 groups of 4 XCDs, runs of 16 per half
-    case KMWS_SCHED_IN_ORDER: *sp = {1u, 0u, 1u}; return true;
-    case KMWS_SCHED_SPLIT2: *sp = {2u, 0u, 1u}; return true;
-    case KMWS_SCHED_SPLIT8: *sp = {8u, 0u, 1u}; return true;
-    case KMWS_SCHED_XCD_RUNS: *sp = {8u, 16u, 1u}; return true;
-    case KMWS_SCHED_SPLIT4: *sp = {4u, 0u, 1u}; return true;
-    default: return false;
-    }
 }
 
 static bool valid_schedule(uint32_t code)
@@ -609,27 +680,28 @@ static kmws_status launch_apply(uint32_t code, uint8_t* base, uint64_t span, con
     if (st != KMWS_OK) return st;
     if (n == 0 || span == 0) return KMWS_OK;
     const WsHead* head = static_cast<const WsHead*>(workspace);
-    const uint32_t* map = reinterpret_cast<const uint32_t*>(head + 1);
+    const TileRec* map = reinterpret_cast<const TileRec*>(head + 1);
     const uint64_t nfull = span / ProdCfg::kTile;
     const bool temporal = temporal_stores(code);
     // a launch may hold at most 2^32 work-items: huge spans go in pieces of blocks
     constexpr uint64_t kMaxBlocks = (1ull << 32) / kBlock / 2;
     const unsigned lds_pad = unmask_lds_pad(span, n);
+    const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
     for (uint64_t b0 = 0; b0 < nfull; b0 += kMaxBlocks) {
         const dim3 grid((uint32_t)(nfull - b0 < kMaxBlocks ? nfull - b0 : kMaxBlocks));
-        const uint32_t nf = (uint32_t)nfull, bb = (uint32_t)b0;
+        const uint32_t bb = (uint32_t)b0;
         if (lds_pad && !temporal)
             hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, true, true>), grid, dim3(kBlock), lds_pad, s, base, descs,
-                               n, map, head, nf, sp.k, sp.c, bb, sp.w);
+                               n, map, head, tm, bb);
         else if (lds_pad)
             hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, true, false>), grid, dim3(kBlock), lds_pad, s, base,
-                               descs, n, map, head, nf, sp.k, sp.c, bb, sp.w);
+                               descs, n, map, head, tm, bb);
         else if (!temporal)
             hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, false, true>), grid, dim3(kBlock), 0, s, base, descs, n,
-                               map, head, nf, sp.k, sp.c, bb, sp.w);
+                               map, head, tm, bb);
         else
             hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, false, false>), grid, dim3(kBlock), 0, s, base, descs,
-                               n, map, head, nf, sp.k, sp.c, bb, sp.w);
+                               n, map, head, tm, bb);
     }
     if (ntiles > nfull)  // the partial last tile
         hipLaunchKernelGGL(unmask_tail_kernel<kUnmaskV>, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, map, head,
@@ -671,7 +743,7 @@ extern "C" {
 size_t kmws_unmask_workspace_size(uint64_t span)
 {
     const uint64_t ntiles = (span + ProdCfg::kTile - 1) / ProdCfg::kTile;
-    return sizeof(WsHead) + (size_t)(ntiles + 1) * sizeof(uint32_t);  // + the map's sentinel
+    return sizeof(WsHead) + (size_t)(ntiles + 1) * sizeof(TileRec);  // + the map's sentinel
 }
 
 kmws_status kmws_unmask_batch(uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
@@ -726,7 +798,7 @@ kmws_status kmws_unpack_unmask(uint8_t* wire, uint64_t wire_len, const uint64_t*
     kmws::note_device_batch(2 * wire_len, s);
     hipLaunchKernelGGL(unpack_plan_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, wire, wire_len, hdr_off,
                        n, mode, out_desc, out_flags, out_err, ilog2_u64(ProdCfg::kTile),
-                       reinterpret_cast<uint32_t*>(head + 1), head);
+                       reinterpret_cast<TileRec*>(head + 1), head);
     st = hip_status(hipGetLastError());
     if (st != KMWS_OK) return st;
     return launch_apply(code, wire, wire_len, out_desc, n, workspace, workspace_bytes, s);
@@ -789,6 +861,20 @@ kmws_status kmws_read_status(const void* workspace, uint32_t* status_out, void* 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return hip_status(e);
 }
+
+#ifdef KMWS_DIAG_PHASE_STAMPS
+// Diagnostic build only: the side buffer of the block-phase stamps, `slots`
+// records of kDiagStamps u64 each (slot = block index / kDiagEvery); null stops
+// the stamping blocks from writing.  Synchronizes.
+kmws_status kmws_diag_set_stamps(uint64_t* buf, uint32_t slots)
+{
+    const uint32_t s = buf ? slots : 0u;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag_slots), &s, sizeof(s)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_diag_stamps), &buf, sizeof(buf)) != hipSuccess)
+        return KMWS_ERR_FAILED;
+    return hip_status(hipDeviceSynchronize());
+}
+#endif
 
 int kmws_device_count(void)
 {
