@@ -111,7 +111,7 @@ def test_encode_parity(T, kind, aligned, room):
     assert st == 0 and total == len(want)
     assert np.array_equal(off[:n].astype(np.uint64), want_off) and off[n] == len(want)
     assert np.array_equal(got[:total], want)
-    assert (got[total:total + 16] == 0xEE).all()  # nothing written past the wire
+    assert len(got) > total and (got[total:] == 0xEE).all()  # nothing written past the wire, anywhere
 
 
 def test_encode_rejects_small_dst(T):
