@@ -466,6 +466,67 @@ kmws_status kmws_find_headers_streams(const uint8_t* wire, uint64_t wire_len, co
                                       uint32_t n_streams, uint64_t* hdr_off, uint32_t cap, uint32_t* n_out,
                                       uint64_t* consumed, void* stream);
 
+/* ---- UTF-8 validation of text messages (opt-in; RFC 6455 5.6 / 8.1) ----
+ * kuma hands text payloads to the application as they are (onWsFrame,
+ * WebSocketImpl.cpp:268-301); a server that wants the check the RFC asks for
+ * (fail the connection with 1007) calls this on the device batch instead of
+ * walking every unmasked payload on the host.  Nothing else changes behaviour.
+ *
+ * Per-frame result: */
+#define KMWS_UTF8_NOT_TEXT  0  /* not checked: control frame, frame of a binary or RSV1 message,
+                                  CONTINUE with no open message */
+#define KMWS_UTF8_OK        1  /* checked; the message's bytes through this frame are a prefix of a
+                                  well-formed UTF-8 string, and a whole one if this frame has FIN */
+#define KMWS_UTF8_BAD       2  /* the first frame of its message at which that stops holding */
+#define KMWS_UTF8_AFTER_BAD 3  /* a later frame of a message already reported BAD (this batch or,
+                                  through the carry, an earlier one) */
+
+/* State of one stream between two batches: 8 bytes, all zero = between messages, otherwise
+ * opaque; pass back what the previous call wrote for that stream. */
+typedef struct kmws_utf8_carry { uint8_t b[8]; } kmws_utf8_carry;
+
+/* Workspace bytes for kmws_utf8_validate: kmws_unmask_workspace_size(span) plus
+ * about 12 B per frame and 8 B per stream. */
+size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
+
+/* Stream-ordered, no host sync, no allocation, kernel nodes only (capturable).
+ * descs / base / span: kmws_unmask_batch's preconditions (sorted, non-
+ * overlapping, in span; base 16-byte aligned); a violation sets status bit 1
+ * and out / carry_out are then not valid.  The payload is never written.
+ * flags[i]: header byte 0 | mask << 8, what kmws_unpack_headers writes to
+ * out_flags.  payload_masked != 0: the bytes in memory are still masked with
+ * descs[i].key (as before an unmask; the key is applied in registers);
+ * == 0: they are plain and key is ignored -- so the call runs before or after
+ * kmws_unmask_batch / kmws_unpack_unmask, or on kmws_gather_unmask's dense
+ * output with descriptors built from dst_off.
+ * stream_first: n_streams + 1 ascending frame indices, [0] == 0, [n_streams]
+ * == n; stream s is frames [stream_first[s], stream_first[s+1]) in wire order
+ * and may be empty; NULL with n_streams == 1: the batch is one stream.  A
+ * malformed array sets status bit 1.  carry_in (may be NULL: every stream
+ * starts between messages) and carry_out (may be NULL) hold one entry per
+ * stream; an empty stream's carry_out equals its carry_in.  n == 0: KMWS_OK,
+ * carry_out = carry_in.  out: n bytes.
+ *
+ * Per stream, in frame order: a control frame (opcode >= 8) gets 0 and does
+ * not touch the message state; opcode 1-7 starts a message, replacing any
+ * unfinished one (whether that is a protocol error is the parser's business),
+ * which is checked iff opcode == 1 and RSV1 == 0 (a compressed message's bytes
+ * are deflate data); opcode 0 belongs to the open message (none: 0); FIN on a
+ * non-control frame closes the message.  Well-formed: RFC 3629 section 4 /
+ * Unicode table 3-7.  A frame is BAD iff it is the first of its message at
+ * which (a) the message's bytes through that frame are not a prefix of any
+ * well-formed string, or (b) it has FIN and they end inside a code point --
+ * which an empty FIN frame can do.
+ *
+ * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
+ * checks it); the byte offset of the error; kmws_decoder_feed / RxLoop and the
+ * resident grid do not call this yet; no fused unmask-and-validate pass. */
+kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
+                               const uint16_t* flags, uint32_t n, int payload_masked,
+                               const uint32_t* stream_first, uint32_t n_streams,
+                               const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                               uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- host-resident batches: pinned H2D -> kernel -> D2H pipeline ---- */
 typedef struct kmws_pipeline kmws_pipeline;
 

@@ -171,6 +171,15 @@ inline kmws_status hip_status(hipError_t e)
 // instead of zero when the graph was replayed after other work on the device).
 kmws_status launch_zero(void* p, uint32_t bytes, hipStream_t s);
 
+// The unmask plan (kmws_unmask.hip), for the other passes over a batch's tiles
+// (kmws_utf8.hip): zeroes the workspace's WsHead, validates the descriptors
+// (kStatusBadDesc) and writes one TileRec per kPlanTile bytes of [0, span), plus
+// the sentinel, behind the WsHead.  KMWS_ERR_BUFFER_TOO_SMALL below
+// kmws_unmask_workspace_size(span) bytes.
+constexpr uint64_t kPlanTile = 16384;
+kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n, void* workspace, size_t ws_bytes,
+                        hipStream_t s);
+
 // Small host batches (the decoder's staging, kmws_unmask.hip): one block per
 // piece of at most kPieceWords 16-byte words of one frame's aligned hull.
 constexpr uint32_t kPieceWords = 4 * kBlock;  // 16 KiB

@@ -614,8 +614,10 @@ static kmws_status check_ws(uint64_t span, size_t ws_bytes, uint64_t* ntiles_out
     return KMWS_OK;
 }
 
-static kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n, void* workspace, size_t ws_bytes,
-                               hipStream_t s)
+static_assert(ProdCfg::kTile == kPlanTile, "the plan's tile is the apply's");
+
+kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n, void* workspace, size_t ws_bytes,
+                        hipStream_t s)
 {
     uint64_t ntiles = 0;
     kmws_status st = check_ws(span, ws_bytes, &ntiles);

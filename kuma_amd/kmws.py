@@ -47,7 +47,10 @@ EXPORTS = [
     "kmws_tx_batch_create", "kmws_tx_batch_destroy", "kmws_tx_batch_add", "kmws_tx_batch_flush",
     "kmws_tx_batch_pending", "kmws_tx_batch_attach_ring", "kmws_host_alloc", "kmws_host_free",
     "kmws_set_device_policy", "kmws_set_thread_device", "kmws_thread_device", "kmws_thread_attach",
+    "kmws_utf8_workspace_size", "kmws_utf8_validate",
 ]
+# per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
+UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
 #: every function include/kmws_bench.h declares (bench / test support, same library)
 BENCH_EXPORTS = [
     "kmws_arena_alloc", "kmws_arena_free", "kmws_arena_place", "kmws_fill_synthetic", "kmws_fill_uniform_descs",
@@ -189,6 +192,8 @@ def bind(L: C.CDLL) -> C.CDLL:
                                                C.POINTER(C.c_uint64)]),
         "kmws_device_policy_pick": (i32, [i32, i32, C.POINTER(C.c_int), i32, u32]),
         "kmws_device_numa_node": (i32, [i32, C.POINTER(C.c_int)]),
+        "kmws_utf8_workspace_size": (sz, [u64, u32, u32]),
+        "kmws_utf8_validate": (i32, [u8p, u64, vp, vp, u32, i32, vp, u32, vp, vp, u8p, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -866,6 +871,44 @@ def gather_unmask(src, descs, dst, dst_off, ws: Workspace, stream=None, check: b
                                     _stream_handle(stream)), "kmws_gather_unmask")
     if check and n:
         _raise_on_status(ws, stream, "kmws_gather_unmask", "dst_off")
+
+
+def utf8_workspace_size(span: int, n: int, n_streams: int = 1) -> int:
+    return lib().kmws_utf8_workspace_size(span, n, n_streams)
+
+
+def utf8_validate(base, descs, flags, out, ws: Workspace, span: Optional[int] = None, masked: bool = False,
+                  stream_first=None, carry_in=None, carry_out=None, stream=None) -> None:
+    """kmws_utf8_validate (stream-ordered): out (uint8, n) receives UTF8_NOT_TEXT /
+    UTF8_OK / UTF8_BAD / UTF8_AFTER_BAD per frame; base is only read.  descs
+    (n, 2) int64, flags int16 (n,) as unpack_headers writes them; masked: the
+    payload bytes are still masked with the descriptors' keys.  stream_first:
+    int32 (n_streams + 1,) ascending frame indices (None: one stream);
+    carry_in / carry_out: uint8 (n_streams, 8) stream states between batches
+    (None: between messages / not wanted).  out and carry_out are valid only
+    when the workspace status is 0 afterwards."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(base, "base", 1, dev)
+    _check_tensor(flags, "flags", 2, dev, n)
+    _check_tensor(out, "out", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = 1
+    if stream_first is not None:
+        _check_tensor(stream_first, "stream_first", 4, dev, 2)
+        ns = stream_first.numel() - 1
+    for name, c in (("carry_in", carry_in), ("carry_out", carry_out)):
+        if c is not None:
+            _check_tensor(c, name, 1, dev, 8 * ns)
+    span = base.numel() if span is None else span
+    if span > base.numel():
+        raise ValueError(f"span {span} exceeds base ({base.numel()} bytes)")
+    _check(lib().kmws_utf8_validate(base.data_ptr(), span, descs.data_ptr(), flags.data_ptr(), n, int(bool(masked)),
+                                    stream_first.data_ptr() if stream_first is not None else None, ns,
+                                    carry_in.data_ptr() if carry_in is not None else None,
+                                    carry_out.data_ptr() if carry_out is not None else None,
+                                    out.data_ptr(), ws.ptr, ws.nbytes, _stream_handle(stream)),
+           "kmws_utf8_validate")
 
 
 def _opt(t):
