@@ -404,7 +404,9 @@ size_t kmws_unpack_workspace_size(void);
  * including the 127-class length quirk.  Per frame: out_desc = {payload
  * offset in wire, len, key (0 if unmasked)}, out_flags = header byte 0 |
  * mask << 8 (may be NULL), out_err = WSError (may be NULL): 1 truncated,
- * 6 bad length, 7 protocol error, 5 frame overruns the next header.  Error
+ * 6 bad length, 7 protocol error, 5 frame overruns the next header -- in the
+ * reference's order: a non-FIN control byte is 7 even as the wire's last byte
+ * (HDR1, :126-130), every other rule waits for the bytes it reads.  Error
  * frames get len 0.  Any error sets status bit 2. */
 kmws_status kmws_unpack_headers(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
                                 int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
@@ -445,8 +447,12 @@ kmws_status kmws_unpack_gather(const uint8_t* wire, uint64_t wire_len, const uin
 /* Host: walk the header chain of a wire image (WSHandler.cpp:108-280 state
  * order, reading only header bytes and skipping payloads) and record each
  * header offset.  Stops after `cap` frames, after a frame that is truncated
- * or has an invalid length (recorded, so kmws_unpack_headers reports it), or
- * after a CLOSE frame (the reference stops parsing there, :265-268).
+ * or has an invalid length -- a 126-class length below 126, a 127-class length
+ * with bit 63 set or above KMWS_MAX_FRAME_DATA_LENGTH, where the reference
+ * returns INVALID_LENGTH (:166-170, :183-193) -- (recorded, so
+ * kmws_unpack_headers reports it), or after a CLOSE frame (the reference stops
+ * parsing there, :265-268).  The walk has no mode and does not stop at a
+ * protocol error (kmws_unpack_headers reports those per frame).
  * *consumed = bytes covered by the recorded complete frames. */
 kmws_status kmws_find_headers(const uint8_t* wire, uint64_t len, uint64_t* hdr_off, uint32_t cap,
                               uint32_t* n_out, uint64_t* consumed);

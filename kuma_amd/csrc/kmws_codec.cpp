@@ -71,6 +71,7 @@ kmws_status kmws_find_headers(const uint8_t* wire, uint64_t len, uint64_t* hdr_o
         uint64_t L;
         if (plen == 126) {
             L = ((uint32_t)wire[p + 2] << 8) | wire[p + 3];
+            if (L < 126) break;  // :166-170, INVALID_LENGTH: the reference stops here
         } else if (plen == 127) {
             uint64_t x = 0;
             for (uint32_t k = 0; k < 8; ++k)

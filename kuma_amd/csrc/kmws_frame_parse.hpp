@@ -113,6 +113,8 @@ __device__ __forceinline__ kmws_desc unpack_one(const uint8_t* __restrict__ wire
     uint32_t b0 = 0, b1 = 0;
     if (h + 2 > wire_len || limit < h || limit > wire_len) {
         err = h + 2 > wire_len ? KMWS_WS_NEED_MORE_DATA : KMWS_WS_INVALID_FRAME;
+        // HDR1 needs one byte: a non-FIN control opcode is rejected before byte 1 is asked for (:126-130)
+        if (h + 1 == wire_len && (hw.x & 0x88u) == 0x08u) err = KMWS_WS_PROTOCOL_ERROR;
     } else {
         b0 = hw.x & 0xFFu;
         b1 = (hw.x >> 8) & 0xFFu;

@@ -1666,6 +1666,7 @@ __device__ __forceinline__ bool walk_step(const uint8_t* __restrict__ wire, uint
     uint64_t L;
     if (plen == 126) {
         L = (byte_of(hw, 2) << 8) | byte_of(hw, 3);
+        if (L < 126) return false;
     } else if (plen == 127) {
         const uint64_t x = ext_len127(hw);
         if ((x >> 63) != 0 || (uint32_t)x > KMWS_MAX_FRAME_DATA_LENGTH) return false;

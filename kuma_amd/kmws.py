@@ -827,18 +827,24 @@ def pack_headers(descs, flags, hdr, hdr_len=None, wire_off=None, ws: Optional[Wo
         _raise_on_status(ws, stream, "kmws_pack_headers", "wire_off")
 
 
-def find_headers_streams(wire, stream_off, cap: int, wire_len: Optional[int] = None, stream=None):
+def find_headers_streams(wire, stream_off, cap: int, wire_len: Optional[int] = None, stream=None, hdr=None):
     """kmws_find_headers_streams: the header-chain walk of every stream
     wire[stream_off[s]:stream_off[s+1]] on the device, one lane per stream.
     Returns (hdr_off (n_streams, cap) int64 absolute offsets, n_out int32,
-    consumed int64) device tensors."""
+    consumed int64) device tensors.  hdr: a caller-owned (n_streams, cap) int64
+    tensor to receive the offsets (a row's entries past its n_out keep their contents)."""
     import torch
     _check_tensor(stream_off, "stream_off", 8, wire.device)
     if stream_off.dtype != torch.int64:
         raise TypeError("stream_off must be int64")
     ns = stream_off.shape[0] - 1
     wire_len = wire.numel() if wire_len is None else wire_len
-    hdr = torch.empty((ns, max(cap, 1)), dtype=torch.int64, device=wire.device)
+    if hdr is None:
+        hdr = torch.empty((ns, max(cap, 1)), dtype=torch.int64, device=wire.device)
+    else:
+        _check_tensor(hdr, "hdr", 8, wire.device, ns * max(cap, 1))
+        if hdr.dtype != torch.int64:
+            raise TypeError("hdr must be int64")
     n_out = torch.empty(ns, dtype=torch.int32, device=wire.device)
     consumed = torch.empty(ns, dtype=torch.int64, device=wire.device)
     _check(lib().kmws_find_headers_streams(wire.data_ptr(), wire_len, stream_off.data_ptr(), ns, hdr.data_ptr(), cap,
