@@ -526,12 +526,60 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  *
  * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
  * checks it); the byte offset of the error; kmws_decoder_feed / RxLoop and the
- * resident grid do not call this yet; no fused unmask-and-validate pass. */
+ * resident grid do not call this yet; the gather form (kmws_unpack_gather) has
+ * no fused validation (the in-place unmask has: kmws_unmask_utf8_batch below). */
 kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
                                const uint16_t* flags, uint32_t n, int payload_masked,
                                const uint32_t* stream_first, uint32_t n_streams,
                                const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- in-place unmask and UTF-8 validation in one pass over the payload ----
+ * kmws_unmask_batch followed by kmws_utf8_validate reads every payload byte
+ * twice; these entries read it once: the words the unmask stores are validated
+ * from the registers that hold them.
+ *
+ * Workspace bytes: kmws_utf8_workspace_size(span, n, n_streams) plus 4 B per
+ * 16 KiB of span (the still-masked dword before each tile, saved ahead of the
+ * payload pass so that no look-back is read from bytes another block may
+ * already have unmasked). */
+size_t kmws_unmask_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
+
+/* The two contracts composed.  Afterwards base holds exactly what
+ * kmws_unmask_batch(base, span, descs, n, ..) leaves: every frame unmasked
+ * whatever its opcode, key-0 frames and bytes outside payloads untouched, the
+ * same 16-byte hull rule; out and carry_out hold exactly what
+ * kmws_utf8_validate(.., payload_masked = 1, ..) would have written on the
+ * still-masked batch.  The verdict is advisory: a BAD message is unmasked like
+ * any other.  schedule: a code of kmws_unmask_apply_sched, < 0 = the default;
+ * an invalid code returns KMWS_ERR_INVALID_PARAM.  Stream-ordered, no host
+ * sync, no allocation, kernel nodes only (capturable); the status word is
+ * cleared by a kernel.  With status bit 1 set (descriptors or stream_first
+ * malformed) nothing is stored to the payload and out / carry_out are not
+ * valid.  Arguments are checked as kmws_utf8_validate checks them, in its
+ * order and with its return values; KMWS_ERR_NOT_SUPPORTED without a gfx950
+ * device (no CPU fallback).  n == 0: KMWS_OK, carry_out = carry_in. */
+kmws_status kmws_unmask_utf8_batch(uint8_t* base, uint64_t span, const kmws_desc* descs,
+                                   const uint16_t* flags, uint32_t n,
+                                   const uint32_t* stream_first, uint32_t n_streams,
+                                   const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                   uint8_t* out, void* workspace, size_t workspace_bytes,
+                                   int schedule, void* stream);
+
+/* kmws_unpack_unmask with the validation in its payload pass.  out_desc,
+ * out_flags (required here), out_err, the wire bytes and status bits 1 and 2
+ * are exactly as after kmws_unpack_unmask; out_utf8 and carry_out are exactly
+ * kmws_utf8_validate applied to the out_desc / out_flags this call writes.  A
+ * frame with a header error is what kmws_unpack_unmask makes of it -- len 0,
+ * flags as parsed -- and is judged as such an empty frame: look at out_err (or
+ * status bit 2) before out_utf8.  workspace:
+ * kmws_unmask_utf8_workspace_size(wire_len, n, n_streams). */
+kmws_status kmws_unpack_unmask_utf8(uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off,
+                                    uint32_t n, int mode, kmws_desc* out_desc, uint16_t* out_flags,
+                                    uint8_t* out_err, const uint32_t* stream_first, uint32_t n_streams,
+                                    const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes,
+                                    int schedule, void* stream);
 
 /* ---- host-resident batches: pinned H2D -> kernel -> D2H pipeline ---- */
 typedef struct kmws_pipeline kmws_pipeline;

@@ -19,54 +19,9 @@
 #include "kmws_bench.h"
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
+#include "kmws_unmask_tile.hpp"
 
 namespace kmws {
-
-// Payload store of a tile word: streaming (the default, and what
-// KMWS_SCHED_NT_STORES asks for) or temporal (plain: the line stays in L2 and
-// is written back on eviction).  The streaming store of the capped launches is
-// `nt sc1`: sc1 stores drop the line from the XCD's L2 where plain, sc0 and nt
-// stores keep it, and on the 64 GiB aligned batch `nt sc1` ran 20.57-20.58 ms
-// against 20.65-20.66 for `nt`, with `sc1` and `sc0 sc1` alone behind both
-// (20.81-20.85); every other load policy than `nt` lost or tied (`nt sc1`
-// loads 20.65-20.67, `sc1` and `sc0 sc1` loads 21.95-21.99); the stand-alone
-// probe (tools/policy_probe.hip) ranks the stores the same way.  The packed
-// wire gained too (20.71-20.80 against 21.04-21.14 ms tuned).  Batches of
-// several frames per tile keep `nt`: with `nt sc1` cfg3's Zipf wire lost
-// (2.70-2.72 against 2.655 ms) where 4 KiB fragments gained (5.22-5.25 against
-// 5.27), and a default must not lose on either
-// (profiles/p01_unmask_tilerec_policy_ab.txt).
-// On plain allocations non-temporal stores ran ahead of temporal on every layout -- the
-// aligned arena 0.82 vs 0.76, the packed wire 0.82 vs 0.76, 4 KiB fragments
-// 0.81 vs 0.76, cfg3's Zipf wire 0.81 vs 0.75 of peak
-// (profiles/r03m_unmask_schedule_sweep_plain_nt_fixed.jsonl) -- so temporal
-// stores are only a candidate of the per-batch autotune (round 2 saw them
-// win by 0.3-1 point on one placed aligned arena, r02bz_unmask_store_policy_ab.txt).
-// The policy is a template parameter of the apply grid, chosen on the host.
-// The stores are buffer stores through a per-tile resource with the cache
-// policy as an immediate: written as `if (nt) __builtin_nontemporal_store(..)
-// else *p = ..`, the compiler had merged the two and dropped the hint.
-// Buffer cache-policy immediates (gfx950): bit 0 sc0, bit 1 nt, bit 4 sc1.
-constexpr int kPolPlain = 0, kPolNT = 2, kPolNTSC1 = 18;
-// What KMWS_SCHED_NT_STORES and the default policy emit: `nt sc1` in the capped
-// launches (mean region of a tile or more: nearly every line is written whole),
-// `nt` in the others (several frames per tile: words of headers and gaps are
-// skipped, lines are written in part).
-constexpr int kPolStreamStoreLarge = kPolNTSC1;
-constexpr int kPolStreamStoreSmall = kPolNT;
-constexpr int kPolStreamLoad = kPolNT;  // every payload load
-constexpr int kBufferRsrcWord3 = 0x00020000;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(uint8_t* base, uint64_t lo, uint64_t hi)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(base + lo, (short)0, (int)((hi - lo + 15) & ~15ull), kBufferRsrcWord3);
-}
-
-template <int POL>
-__device__ __forceinline__ void store_word(const u32x4& val, __amdgpu_buffer_rsrc_t rs, uint32_t off)
-{
-    __builtin_amdgcn_raw_buffer_store_b128(val, rs, (int)off, 0, POL);
-}
 
 // Diagnostic build only (KMWS_DIAG_PHASE_STAMPS, kuma_amd/build.py `defines`;
 // loaded by path by tools/block_phases.py, never the product library): one
@@ -99,14 +54,6 @@ __device__ uint32_t g_diag_slots = 0;
 #define KMWS_STAMP(st, i) do { (void)(st); } while (0)
 #define KMWS_STAMP_AFTER(st, i, waitcnt) do { (void)(st); } while (0)
 #endif
-
-// Each lane owns V consecutive-block words: word w = tid + kBlock * i.
-template <int V>
-struct UnmaskCfg {
-    static constexpr int kWords = kBlock * V;
-    static constexpr uint64_t kTile = (uint64_t)kWords * 16u;
-    static constexpr int kCap = kBlock;  // descriptors staged per LDS round
-};
 
 // Frame f's records for the tiles [b0, b1) whose start lies in its region, and
 // the sentinel after the last tile ("next tile's frame" of the last tile).  A
@@ -182,26 +129,6 @@ __global__ void __launch_bounds__(kBlock) unpack_plan_kernel(const uint8_t* __re
     const uint64_t b1 = (next + T - 1) >> tile_shift;
     // df: the descriptor this lane just wrote (empty after a header error)
     write_tile_recs(map, f, n, df.off, df.len, df.key, b0, b1, tile_shift);
-}
-
-// Issue every payload load of a tile.  Full tiles load unconditionally so the
-// loads stay back to back.  Payload is touched once: non-temporal loads and
-// stores (measured +6 % on MI355X for this in-place stream, tools/membw_probe.hip).
-// Buffer loads through the tile's resource, the cache policy a template
-// immediate like the stores' (as fast as the global `nt` loads they replaced:
-// 20.65-20.66 ms both, profiles/p01_unmask_tilerec_policy_ab.txt).
-template <int V, bool FULL, int POL = kPolStreamLoad>
-__device__ __forceinline__ void load_tile(uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
-                                          u32x4 (&v)[V])
-{
-    const int tid = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);  // the stores' resource
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
-        if (FULL || tile_lo + x < tile_hi) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)x, 0, POL);
-        else v[i] = u32x4{0, 0, 0, 0};
-    }
 }
 
 // Mask and store a loaded tile.  rec, rec_next = the plan records of the tile
@@ -554,10 +481,6 @@ __global__ void __launch_bounds__(kBlock) check_unmasked_kernel(const uint8_t* _
     if (bad) atomicAdd(mismatches, bad);
 }
 
-// Tile geometry used by the product path (tuned on MI355X).
-constexpr int kUnmaskV = 4;
-using ProdCfg = UnmaskCfg<kUnmaskV>;
-
 // Blocks of an apply grid resident per CU.  Fewer blocks in flight stream HBM
 // better: 2 blocks of 256 lanes per CU (32 KiB of loads in flight per CU) run
 // the 64 GiB batch at 84.5-84.8 % of peak against 82.4-82.9 % with the 6 the
@@ -565,27 +488,30 @@ using ProdCfg = UnmaskCfg<kUnmaskV>;
 // (profiles/r02ag_unmask_occupancy.txt).  The cap is dynamic LDS the kernel does
 // not use: a block asks for just over a third of the CU's LDS.
 constexpr unsigned kUnmaskBlocksPerCu = 2;
-constexpr uint32_t kUnmaskStaticLds = ProdCfg::kCap * (8 + 8 + 4);  // s_off, s_end, s_key
 
-static unsigned unmask_lds_pad_device()
+// Dynamic LDS that lets exactly `blocks_per_cu` blocks of `static_lds` bytes of
+// static LDS share a CU (0 if the device cannot be asked).
+unsigned lds_pad_for(unsigned blocks_per_cu, unsigned static_lds)
 {
     static thread_local int dev_cached = -1;
-    static thread_local unsigned pad = 0;
+    static thread_local unsigned lds_cached = 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (dev != dev_cached) {
         int lds = 0;
-        pad = 0;
+        lds_cached = 0;
         if (
             hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess &&
-            lds > 0) {
-            const unsigned per_block = (unsigned)lds / (kUnmaskBlocksPerCu + 1) + 1;  // one more does not fit
-            pad = per_block > kUnmaskStaticLds ? per_block - kUnmaskStaticLds : 0u;
-        }
+            lds > 0)
+            lds_cached = (unsigned)lds;
         dev_cached = dev;
     }
-    return pad;
+    if (!lds_cached) return 0;
+    const unsigned per_block = lds_cached / (blocks_per_cu + 1) + 1;  // one more does not fit
+    return per_block > static_lds ? per_block - static_lds : 0u;
 }
+
+static unsigned unmask_lds_pad_device() { return lds_pad_for(kUnmaskBlocksPerCu, kUnmaskStaticLds); }
 
 // The cap pays where tiles take the one- or two-frame paths (regions of a tile
 // or more: 16 KiB frames ran 85.5 % capped vs 79-83 % uncapped); batches of
@@ -593,9 +519,11 @@ static unsigned unmask_lds_pad_device()
 // latency hiding of a full CU) keep every block: 8 KiB frames ran 54.8 % capped
 // vs 83 %, 4 KiB frames 47.6 % vs 80 % (profiles/r02at_unmask_framelen_occupancy.txt).
 // Mean region >= 1 tile selects.
+bool unmask_capped(uint64_t span, uint32_t n) { return n && span / n >= ProdCfg::kTile; }
+
 static unsigned unmask_lds_pad(uint64_t span, uint32_t n)
 {
-    return n && span / n >= ProdCfg::kTile ? unmask_lds_pad_device() : 0u;
+    return unmask_capped(span, n) ? unmask_lds_pad_device() : 0u;
 }
 
 static uint32_t ilog2_u64(uint64_t x)
@@ -657,12 +585,12 @@ kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n, void*
 constexpr uint32_t kKindMask = 0xFFu;
 constexpr uint32_t kSchedTemporal = KMWS_SCHED_TEMPORAL_STORES;
 constexpr uint32_t kSchedNT = KMWS_SCHED_NT_STORES;
-static uint32_t default_schedule(uint64_t span, uint32_t n)
+uint32_t default_schedule(uint64_t span, uint32_t n)
 {
     return n && span / n >= ProdCfg::kTile ? KMWS_SCHED_SPLIT4 : KMWS_SCHED_GROUPED_RUNS;
 }
 
-static bool valid_schedule(uint32_t code)
+bool valid_schedule(uint32_t code)
 {
     Split sp;
     const uint32_t store = code & (kSchedTemporal | kSchedNT);
@@ -670,7 +598,7 @@ static bool valid_schedule(uint32_t code)
            (code & ~(kKindMask | kSchedTemporal | kSchedNT)) == 0;
 }
 
-static bool temporal_stores(uint32_t code) { return (code & kSchedTemporal) != 0; }
+bool temporal_stores(uint32_t code) { return (code & kSchedTemporal) != 0; }
 
 static kmws_status launch_apply(uint32_t code, uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
                                 const void* workspace, size_t ws_bytes, hipStream_t s)
@@ -734,6 +662,19 @@ kmws_status launch_unmask_pieces(uint8_t* base, const kmws_desc* descs, const Pi
     if (np == 0) return KMWS_OK;
     if (!base || !descs || !pieces) return KMWS_ERR_INVALID_PARAM;
     hipLaunchKernelGGL(unmask_pieces_kernel, dim3(np), dim3(kBlock), 0, s, base, descs, pieces);
+    return hip_status(hipGetLastError());
+}
+
+kmws_status launch_unpack_plan(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n, int mode,
+                               kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err, void* workspace,
+                               hipStream_t s)
+{
+    WsHead* head = static_cast<WsHead*>(workspace);
+    if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    if (n == 0) return KMWS_OK;
+    hipLaunchKernelGGL(unpack_plan_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, wire, wire_len, hdr_off,
+                       n, mode, out_desc, out_flags, out_err, ilog2_u64(ProdCfg::kTile),
+                       reinterpret_cast<TileRec*>(head + 1), head);
     return hip_status(hipGetLastError());
 }
 }  // namespace kmws

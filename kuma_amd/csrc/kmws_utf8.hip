@@ -29,7 +29,11 @@
 //   5. utf8_finish_kernel: out[i] from first_bad[slot]; carry_out per stream.
 // Nothing is stored to the payload.  Algorithmic bytes: the checked payload
 // read once + ~32 B per frame (descriptor, flags, element, verdict).
+// kmws_unmask_utf8_batch / kmws_unpack_unmask_utf8 (below, "the fused in-place
+// pass") run kernels 1-3 and 5 as they are around a payload pass that also
+// unmasks in place.
 #include "kmws_common.hpp"
+#include "kmws_unmask_tile.hpp"
 #include "kmws_utf8_rule.hpp"
 
 namespace kmws {
@@ -412,10 +416,531 @@ __global__ void __launch_bounds__(kBlock) utf8_carry_copy_kernel(uint32_t ns,
     if (s < ns) store_carry(carry_out, s, load_carry(carry_in, s));
 }
 
+// ---- the fused in-place pass: kmws_unmask_utf8_batch / kmws_unpack_unmask_utf8 ----
+//
+// One kernel family does what unmask_split_kernel / unmask_tail_kernel
+// (kmws_unmask.hip) and utf8_payload_kernel<true> do in two trips over the
+// payload: the tile is loaded once, every word's mask is built by the apply's
+// three paths (the record's rotated key of a covered tile; two block-uniform
+// descriptors in the capped launches; descriptors staged in LDS), the unmasked
+// words are stored with the apply's store policy, and the words of checked
+// frames are validated from the registers that hold them.  On the one- and
+// two-frame paths the stores go first: nothing of the rule stands between a
+// word's arrival and its store, and a tile of unchecked frames (binary, RSV1,
+// control) ends after them on a block-uniform test of its frames' views -- the
+// plain unmask and a scalar load that arrives under the payload.  What follows
+// the stores touches registers, LDS and scalars only, and the stores are
+// straight-line code (kFusedNoStore): a wait on the vector memory counter there
+// would wait for the stores' write-through as well.  The LDS-staged path loads
+// descriptors and views to validate, so it validates first and stores last.
+//
+// The look-back of a word's first byte is the dword before it.  Inside a wave
+// that is the neighbour lane's register.  For lane 0 of a wave, the validator
+// alone may read it from memory; here that dword belongs to another wave or to
+// another block's tile, which may or may not have stored it unmasked already.
+// So no look-back is read from the payload while this kernel runs:
+//   - the dword before each tile comes from utf8_edges_kernel, which saves it,
+//     still masked, ahead of this kernel in stream order (4 B per tile);
+//   - the dword before each of a tile's other fifteen 1 KiB rows is the last
+//     register of lane 63 of the wave that loaded the row before: handed over
+//     in LDS behind one barrier, which stands after the stores and is reached
+//     only by tiles that hold a checked frame.  (The other form, a pre-pass
+//     that saves all sixteen dwords of a tile and a kernel with no barrier, was
+//     built and timed and lost on every kind of payload: each of those dwords
+//     costs the pre-pass a memory request of its own.  DESIGN 4 has the times.)
+// A saved dword is XORed with the frame's rotated key like the words (the dword
+// before a 16-byte word has the word's key phase) and is used only where the
+// frame reaches three bytes back, as word_bad has it.
+constexpr int kFusedRows = (int)(kPlanTile / 1024);  // a wave-instruction loads 1 KiB: row = wave + 4 * i
+// A store that must not happen takes this offset, past every tile's resource,
+// and is dropped by the buffer's range check: the stores stay straight-line
+// code, so the compiler keeps track of which loads have arrived (fused_tile).
+constexpr uint32_t kFusedNoStore = 0x7FFFFFF0u;
+static_assert(kUtf8V == kUnmaskV && kFusedRows == 4 * kUtf8V, "the validator's tile is the apply's");
+
+// Blocks of a capped launch per CU.  The apply streams best with 2 (its stores
+// follow its loads at once); here a block goes on to validate after its stores,
+// and with 2 blocks per CU nothing covers that time: the 4 GiB ASCII batch ran
+// 2.64 ms at 2, 1.86 ms at 3 and 1.47 ms at 4 blocks per CU (mixed text 3.39 /
+// 2.42 / 1.99 ms), the same bytes marked binary 1.29 / 1.36 / 1.39 ms against the
+// unmask's 1.30.  4 is also what the kernel's registers allow.
+constexpr unsigned kFusedBlocksPerCu = 4;
+constexpr unsigned kFusedStaticLds = kUnmaskStaticLds + 4u * (unsigned)kFusedRows;  // + s_row
+
+struct FusedWs {
+    Utf8Ws u;
+    size_t edges, total;
+};
+static FusedWs fused_ws(uint64_t span, uint32_t n, uint32_t n_streams)
+{
+    FusedWs w;
+    w.u = utf8_ws(span, n, n_streams);
+    const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;
+    w.edges = r16(w.u.total);
+    w.total = w.edges + r16((size_t)ntiles * 4);
+    return w;
+}
+
+// edges[t]: the dword before tile t as it lies in memory before the payload
+// pass (tile 0 has none: 0).
+__global__ void __launch_bounds__(kBlock) utf8_edges_kernel(const uint8_t* __restrict__ base,
+                                                            uint32_t* __restrict__ edges, uint32_t ntiles)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t < ntiles) edges[t] = t ? *reinterpret_cast<const uint32_t*>(base + (uint64_t)t * kPlanTile - 4) : 0u;
+}
+
+// The look-back dword of each of the lane's words, still masked: the neighbour
+// lane's last dword, for lane 0 of a wave the row hand-over; edge: the saved
+// dword before the tile (block-uniform).  Has a barrier.
+__device__ __forceinline__ void fused_lookback(const u32x4 (&v)[kUtf8V], uint32_t edge, uint32_t* s_row,
+                                               uint32_t (&prev)[kUtf8V])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 63) {
+#pragma unroll
+        for (int i = 0; i < kUtf8V; ++i) s_row[wave + 4 * i] = v[i].w;  // the end of row wave + 4 * i
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kUtf8V; ++i) {
+        const uint32_t up = __shfl_up(v[i].w, 1);
+        const uint32_t ed = (wave == 0 && i == 0) ? edge : s_row[wave + 4 * i - 1];
+        prev[i] = lane == 0 ? ed : up;
+    }
+}
+
+// Word i of the lane (w, prev: as loaded, masked) against frame g = [off, end)
+// with rotated key r and view gv: reports the frame if the rule rejects a byte
+// of it in this word.
+__device__ __forceinline__ bool fused_word_frame_bad(const u32x4& v, uint32_t prev, uint64_t a, uint64_t off,
+                                                     uint64_t end, uint32_t r, uint32_t ctx)
+{
+    const u32x4 w = v ^ r;
+    const bool plain = off + 3u <= a && end >= a + 16u && ((w.x | w.y | w.z | w.w) & 0x80808080u) == 0u &&
+                       ((prev ^ r) & 0x80000000u) == 0u;
+    return !plain && word_bad(prev ^ r, w, a, off, end, ctx);
+}
+
+// Mask, store and validate a loaded tile.  rec, rec_next, ok, pre: as
+// finish_tile (kmws_unmask.hip) takes them, and the same three mask paths and
+// store policies; edge: see fused_lookback.
+template <bool FULL, bool TWO, bool NT>
+__device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
+                                           const kmws_desc* __restrict__ d, uint32_t n, TileRec rec, TileRec rec_next,
+                                           bool ok, const u32x4 (&v)[kUtf8V], uint32_t edge,
+                                           const Utf8View* __restrict__ views, uint32_t* __restrict__ first_bad,
+                                           uint64_t* s_off, uint64_t* s_end, uint32_t* s_key, uint32_t* s_row,
+                                           const u32x4* pre)
+{
+    constexpr int V = kUtf8V;
+    using Cfg = UnmaskCfg<V>;
+    constexpr int SP = !NT ? kPolPlain : (TWO ? kPolStreamStoreLarge : kPolStreamStoreSmall);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);
+
+    // One frame covers the tile: the record holds the whole mask.  No
+    // descriptor, LDS or barrier before the stores; whether the frame is
+    // checked is one scalar load that arrives under them.
+    if (FULL && tile_rec_covered(rec, n)) {
+        const uint32_t r = rec.rkey;
+        const uint32_t f = tile_rec_frame(rec, n);
+        // the frame's view and descriptor: two scalar loads that depend on the
+        // record alone, issued together and under the payload (a bad plan's
+        // record may hold anything: the index stays in range)
+        const uint32_t fi = f < n ? f : 0u;
+        const Utf8View fv = views[fi];
+        const kmws_desc d0 = d[fi];
+        // A bad plan stores nothing: its stores go through a resource of no
+        // bytes, which drops them.  Not `if (ok)`: after a branch around the
+        // stores the compiler no longer knows that the loads have arrived, and
+        // waits for the whole memory queue -- the stores' write-through included
+        // -- at the next use of a loaded word (the ASCII batch ran 2.86 ms so,
+        // DESIGN 4).
+        const __amdgpu_buffer_rsrc_t rs_ok = __builtin_amdgcn_make_buffer_rsrc(
+            base + tile_lo, (short)0, ok ? (int)Cfg::kTile : 0, kBufferRsrcWord3);
+        // each word is stored when it arrives, and nothing of what follows -- the
+        // wait for the view and the descriptor least of all -- moves up between
+        // or ahead of the stores
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            __builtin_amdgcn_sched_barrier(0);
+            store_word<SP>(v[i] ^ r, rs_ok, 16u * (uint32_t)(tid + kBlock * i));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // block-uniform: binary, RSV1 and control tiles end here (a covering
+        // frame is never empty and never starts past the tile's first byte)
+        if (!ok | (f >= n) | !(fv.w & kUtf8Checked) | (d0.len == 0u) | (d0.off > tile_lo)) return;
+        const uint64_t end = d0.off + d0.len;
+        uint32_t prev[V];
+        fused_lookback(v, edge, s_row, prev);
+        // a word of ASCII bytes after an ASCII byte is decided by one OR and a test
+        bool slow[V];
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
+            const u32x4 w = v[i] ^ r;
+            const uint32_t hb = (w.x | w.y | w.z | w.w) & 0x80808080u;
+            slow[i] = hb != 0u || ((prev[i] ^ r) & 0x80000000u) != 0u || a < d0.off + 3u;
+            any |= slow[i];
+        }
+        bool bad = false;
+        if (__any(any)) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
+                if (slow[i]) bad |= word_bad(prev[i] ^ r, v[i] ^ r, a, d0.off, end, fv.w);
+            }
+        }
+        const unsigned long long m = __ballot(bad);  // one report per wave
+        if (m != 0ull && lane == __ffsll((long long)m) - 1) report_bad(first_bad, fv.slot, f);
+        return;
+    }
+
+    // frames [f0, flast] are the only ones that can overlap the tile
+    const uint32_t f0 = tile_rec_frame(rec, n);
+    const uint32_t flast = tile_rec_frame(rec_next, n);
+    const kmws_desc d0 = d[f0 < n ? f0 : 0];
+
+    // Two frames at most, in the capped launches: both descriptors are
+    // block-uniform scalars, every mask is built before the first store.
+    if (TWO && FULL && flast <= f0 + 1 && f0 < n) {
+        const bool two = flast > f0 && flast < n;
+        const kmws_desc d1 = two ? d[flast] : kmws_desc{~0ull, 0u, 0u};
+        const uint32_t r0 = rot_key(d0.key, d0.off), r1 = rot_key(d1.key, d1.off);
+        constexpr uint32_t T = (uint32_t)Cfg::kTile;
+        auto rel = [&](uint64_t x) -> uint32_t {
+            return x <= tile_lo ? 0u : (x - tile_lo >= T ? T : (uint32_t)(x - tile_lo));
+        };
+        const uint32_t s0 = rel(d0.off), t0 = rel(d0.off + d0.len);
+        const uint32_t s1 = rel(d1.off), t1 = d1.len ? rel(d1.off + d1.len) : s1;
+        u32x4 m[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
+            u32x4 mm = u32x4{0, 0, 0, 0};
+            if (s0 <= x && t0 >= x + 16) {
+                mm = u32x4{r0, r0, r0, r0};
+            } else if (s1 <= x && t1 >= x + 16) {
+                mm = u32x4{r1, r1, r1, r1};
+            } else {  // a word holding a frame edge: byte-exact
+                auto cl = [&](uint32_t y) -> int { return y <= x ? 0 : (y - x >= 16u ? 16 : (int)(y - x)); };
+                mm = (word_byte_range(cl(s0), cl(t0)) & r0) | (word_byte_range(cl(s1), cl(t1)) & r1);
+            }
+            m[i] = mm;
+        }
+        // the two views: scalar loads beside the descriptors', used after the stores
+        const Utf8View v0 = views[f0];
+        const Utf8View v1 = two ? views[flast] : Utf8View{0u, 0u};
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const bool st = ok && (m[i].x | m[i].y | m[i].z | m[i].w) != 0u;
+            store_word<SP>(v[i] ^ m[i], rs, st ? 16u * (uint32_t)(tid + kBlock * i) : kFusedNoStore);
+        }
+        if (!ok) return;
+        const bool c0 = (v0.w & kUtf8Checked) != 0u && t0 > s0, c1 = (v1.w & kUtf8Checked) != 0u && t1 > s1;
+        if (!c0 && !c1) return;  // block-uniform
+        uint32_t prev[V];
+        fused_lookback(v, edge, s_row, prev);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
+            const uint64_t a = tile_lo + x;
+            if (c0 && s0 < x + 16 && t0 > x &&
+                fused_word_frame_bad(v[i], prev[i], a, d0.off, d0.off + d0.len, r0, v0.w))
+                report_bad(first_bad, v0.slot, f0);
+            if (c1 && s1 < x + 16 && t1 > x &&
+                fused_word_frame_bad(v[i], prev[i], a, d1.off, d1.off + d1.len, r1, v1.w))
+                report_bad(first_bad, v1.slot, flast);
+        }
+        return;
+    }
+
+    // General path: the descriptors of the frames overlapping the tile staged
+    // in LDS, kCap per round, a byte-exact mask per 16-byte word.
+    u32x4 m[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) m[i] = u32x4{0, 0, 0, 0};
+    uint32_t f = f0;
+    auto round = [&](bool have, const u32x4& x) -> int {
+        int valid = 0;
+        if (have) {
+            const uint64_t off = (uint64_t)x.x | ((uint64_t)x.y << 32);
+            if (off < tile_hi) {
+                valid = 1;
+                s_off[tid] = off;
+                s_end[tid] = off + x.z;
+                s_key[tid] = x.w;
+            }
+        }
+        const int cnt = __syncthreads_count(valid);  // sorted => a prefix
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
+            int lo = 0, hi = cnt;  // first staged frame with end > a
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_end[mid] <= a) lo = mid + 1; else hi = mid;
+            }
+            for (int j = lo; j < cnt; ++j) {
+                const uint64_t o = s_off[j];
+                if (o >= a + 16) break;
+                const uint64_t e = s_end[j];
+                const uint32_t r = rot_key(s_key[j], o);
+                if (o <= a && e >= a + 16) {
+                    m[i] |= u32x4{r, r, r, r};
+                } else {
+                    const int blo = o > a ? (int)(o - a) : 0;
+                    const int bhi = e < a + 16 ? (int)(e - a) : 16;
+                    m[i].x |= r & dword_byte_mask(blo, bhi, 0);
+                    m[i].y |= r & dword_byte_mask(blo, bhi, 1);
+                    m[i].z |= r & dword_byte_mask(blo, bhi, 2);
+                    m[i].w |= r & dword_byte_mask(blo, bhi, 3);
+                }
+            }
+        }
+        __syncthreads();  // every lane done reading this round's LDS
+        return cnt;
+    };
+    auto have_f = [&]() { return f + (uint32_t)tid < n && f + (uint32_t)tid <= flast; };
+    auto load_f = [&]() { return have_f() ? *reinterpret_cast<const u32x4*>(d + f + tid) : u32x4{0, 0, 0, 0}; };
+    int cnt = pre ? round(have_f(), *pre) : round(have_f(), load_f());
+    while (cnt == Cfg::kCap) {
+        f += Cfg::kCap;
+        cnt = round(have_f(), load_f());
+    }
+    // Validation of the words of checked frames, as utf8_payload_kernel's
+    // general path: each word finds its frames in the sorted descriptors.
+    bool any = false;
+    uint32_t fl = flast >= n ? n - 1 : flast;
+    if (fl < f0) fl = f0;
+    if (ok && f0 < n)
+        for (uint32_t g = f0 + (uint32_t)tid; g <= fl; g += kBlock) any |= (views[g].w & kUtf8Checked) != 0u;
+    if (__syncthreads_or(any)) {
+        uint32_t prev[V];
+        fused_lookback(v, edge, s_row, prev);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
+            if (a >= tile_hi) continue;
+            uint32_t gl = f0, gh = fl + 1u;  // the first frame that ends after a
+            while (gl < gh) {
+                const uint32_t mid = gl + (gh - gl) / 2;
+                const kmws_desc dm = d[mid];
+                if (dm.off + dm.len <= a) gl = mid + 1; else gh = mid;
+            }
+            for (uint32_t g = gl; g <= fl; ++g) {
+                const kmws_desc dg = d[g];
+                if (dg.off >= a + 16u) break;
+                if (dg.len == 0u) continue;
+                const Utf8View gv = views[g];
+                if (!(gv.w & kUtf8Checked)) continue;
+                if (fused_word_frame_bad(v[i], prev[i], a, dg.off, dg.off + dg.len, rot_key(dg.key, dg.off), gv.w))
+                    report_bad(first_bad, gv.slot, g);
+            }
+        }
+    }
+    // The stores come last here: the validation above loads descriptors and
+    // views, and a load's wait also waits for every store issued before it.
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
+        const u32x4 mm = m[i];
+        const bool st = ok && (mm.x | mm.y | mm.z | mm.w) != 0u;  // past a partial tile's end the resource drops it
+        store_word<SP>(v[i] ^ mm, rs, st ? x : kFusedNoStore);
+    }
+}
+
+// One block per full tile, the apply's grid (unmask_split_kernel): the same
+// block -> tile mapping, metadata loads ahead of the payload loads, and in the
+// uncapped launches the tile's descriptors ahead of both.
+template <bool TWO, bool NT>
+__global__ void __launch_bounds__(kBlock) unmask_utf8_split_kernel(uint8_t* __restrict__ base,
+                                                                   const kmws_desc* __restrict__ d, uint32_t n,
+                                                                   const TileRec* __restrict__ map,
+                                                                   const WsHead* __restrict__ head,
+                                                                   const Utf8View* __restrict__ views,
+                                                                   uint32_t* __restrict__ first_bad,
+                                                                   const uint32_t* __restrict__ edges, TileMapping tm,
+                                                                   uint32_t b0)
+{
+    using Cfg = UnmaskCfg<kUtf8V>;
+    __shared__ uint64_t s_off[Cfg::kCap];
+    __shared__ uint64_t s_end[Cfg::kCap];
+    __shared__ uint32_t s_key[Cfg::kCap];
+    __shared__ uint32_t s_row[kFusedRows];
+    const uint32_t tile = tile_of_block(b0 + blockIdx.x, tm);
+    const uint64_t lo = (uint64_t)tile * Cfg::kTile;
+    const TileRecPair recs = *reinterpret_cast<const TileRecPair*>(map + tile);
+    const TileRec rec = recs.at, rec_next = recs.next;
+    const uint32_t status = head->status;
+    const uint32_t edge = edges[tile];  // block-uniform: a scalar load, ahead of the payload
+    u32x4 v[kUtf8V];
+    if constexpr (!TWO) {
+        const uint32_t f = tile_rec_frame(rec, n), fl = tile_rec_frame(rec_next, n);
+        const uint32_t fi = f + threadIdx.x;
+        u32x4 pre = u32x4{0, 0, 0, 0};
+        if (fi < n && fi <= fl) pre = *reinterpret_cast<const u32x4*>(d + fi);
+        load_tile<kUtf8V, true>(base, lo, lo + Cfg::kTile, v);
+        __builtin_amdgcn_sched_barrier(0);
+        fused_tile<true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, (status & kStatusBadDesc) == 0, v,
+                                  edge, views, first_bad, s_off, s_end, s_key, s_row, &pre);
+        return;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_tile<kUtf8V, true>(base, lo, lo + Cfg::kTile, v);
+    __builtin_amdgcn_sched_barrier(0);
+    fused_tile<true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, (status & kStatusBadDesc) == 0, v, edge,
+                              views, first_bad, s_off, s_end, s_key, s_row, nullptr);
+}
+
+// One block for the partial last tile of a span.
+__global__ void __launch_bounds__(kBlock) unmask_utf8_tail_kernel(uint8_t* __restrict__ base, uint64_t span,
+                                                                  const kmws_desc* __restrict__ d, uint32_t n,
+                                                                  const TileRec* __restrict__ map,
+                                                                  const WsHead* __restrict__ head,
+                                                                  const Utf8View* __restrict__ views,
+                                                                  uint32_t* __restrict__ first_bad,
+                                                                  const uint32_t* __restrict__ edges, uint32_t tile)
+{
+    using Cfg = UnmaskCfg<kUtf8V>;
+    __shared__ uint64_t s_off[Cfg::kCap];
+    __shared__ uint64_t s_end[Cfg::kCap];
+    __shared__ uint32_t s_key[Cfg::kCap];
+    __shared__ uint32_t s_row[kFusedRows];
+    const uint64_t tile_lo = (uint64_t)tile * Cfg::kTile;
+    const uint32_t edge = edges[tile];  // block-uniform: a scalar load, ahead of the payload
+    u32x4 v[kUtf8V];
+    load_tile<kUtf8V, false>(base, tile_lo, span, v);
+    __builtin_amdgcn_sched_barrier(0);
+    fused_tile<false, false, true>(base, tile_lo, span, d, n, map[tile], map[tile + 1],
+                                   (head->status & kStatusBadDesc) == 0, v, edge, views, first_bad, s_off, s_end,
+                                   s_key, s_row, nullptr);
+}
+
 static bool have_device()
 {
     static const bool have = kmws_device_count() > 0;
     return have;
+}
+
+// The per-frame kernels of a batch (1-3 of the list above) and the finish (5),
+// on a workspace laid out by utf8_ws behind a plan that has been launched.
+struct Utf8Arrays {
+    WsHead* head;
+    const TileRec* map;
+    uint32_t* first_bad;
+    Utf8Elem *elems, *aggs, *pre, *carry_tmp;
+    const Utf8View* views;
+};
+static Utf8Arrays utf8_arrays(void* workspace, const Utf8Ws& w)
+{
+    uint8_t* wsb = static_cast<uint8_t*>(workspace);
+    Utf8Arrays a;
+    a.head = static_cast<WsHead*>(workspace);
+    a.map = reinterpret_cast<const TileRec*>(a.head + 1);
+    a.first_bad = reinterpret_cast<uint32_t*>(wsb + w.first_bad);
+    a.elems = reinterpret_cast<Utf8Elem*>(wsb + w.elems);
+    a.aggs = reinterpret_cast<Utf8Elem*>(wsb + w.aggs);
+    a.pre = reinterpret_cast<Utf8Elem*>(wsb + w.pre);
+    a.carry_tmp = reinterpret_cast<Utf8Elem*>(wsb + w.carry);
+    a.views = reinterpret_cast<const Utf8View*>(a.elems);
+    return a;
+}
+static void launch_utf8_frames(const Utf8Ws& w, const Utf8Arrays& a, const uint8_t* base, uint64_t span,
+                               const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
+                               const uint32_t* stream_first, uint32_t n_streams, const kmws_utf8_carry* carry_in,
+                               hipStream_t s)
+{
+    const uint32_t sblk = stream_first ? (n_streams + 1u + kBlock - 1) / kBlock : 0u;
+    hipLaunchKernelGGL(utf8_elem_kernel, dim3(w.nblk > sblk ? w.nblk : sblk), dim3(kBlock), 0, s, base, span, descs,
+                       flags, n, masked, stream_first, n_streams, carry_in, a.elems, a.first_bad, a.aggs, w.nblk,
+                       a.head);
+    hipLaunchKernelGGL(utf8_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, a.aggs, a.pre, w.nblk);
+    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(w.nblk), dim3(kBlock), 0, s, flags, n, stream_first, n_streams, carry_in,
+                       a.elems, a.pre, a.first_bad, a.carry_tmp);
+}
+static void launch_utf8_finish(const Utf8Arrays& a, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                               const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out, hipStream_t s)
+{
+    const uint32_t fin_lanes = carry_out && n_streams > n ? n_streams : n;
+    hipLaunchKernelGGL(utf8_finish_kernel, dim3((fin_lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n,
+                       stream_first, n_streams, a.views, a.first_bad, a.carry_tmp, carry_in, carry_out, out);
+}
+static kmws_status launch_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                     hipStream_t s)
+{
+    if (carry_out && n_streams)
+        hipLaunchKernelGGL(utf8_carry_copy_kernel, dim3((n_streams + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                           n_streams, carry_in, carry_out);
+    return hip_status(hipGetLastError());
+}
+
+// The argument checks the fused entries share with kmws_utf8_validate, in its
+// order; `code`: the schedule to run.
+static kmws_status fused_check(const uint8_t* base, bool ptrs_ok, uint32_t n, const uint32_t* stream_first,
+                               uint32_t n_streams, uint64_t span, int schedule, size_t workspace_bytes,
+                               const FusedWs& w, uint32_t* code)
+{
+    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
+    if (n && !ptrs_ok) return KMWS_ERR_INVALID_PARAM;
+    if (reinterpret_cast<uintptr_t>(base) & 15u) return KMWS_ERR_INVALID_PARAM;
+    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
+    *code = schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule;
+    if (!valid_schedule(*code)) return KMWS_ERR_INVALID_PARAM;
+    if (n && workspace_bytes < w.total) return KMWS_ERR_BUFFER_TOO_SMALL;
+    if (!have_device()) return KMWS_ERR_NOT_SUPPORTED;
+    return KMWS_OK;
+}
+
+// Behind a launched plan (and the header parse, if any): the look-back
+// pre-pass, the per-frame kernels on the still-masked payload, the fused
+// payload pass on the apply's grids, the finish.
+static kmws_status launch_fused(uint32_t code, uint8_t* base, uint64_t span, const kmws_desc* descs,
+                                const uint16_t* flags, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                                const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
+                                void* workspace, const FusedWs& w, hipStream_t s)
+{
+    Split sp;
+    if (!split_of(code & 0xFFu, &sp)) return KMWS_ERR_INVALID_PARAM;
+    const Utf8Arrays a = utf8_arrays(workspace, w.u);
+    uint32_t* edges = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(workspace) + w.edges);
+    const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;  // launch_plan bounded it
+    const uint64_t nfull = span / kPlanTile;
+    if (ntiles)
+        hipLaunchKernelGGL(utf8_edges_kernel, dim3((uint32_t)((ntiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           base, edges, (uint32_t)ntiles);
+    launch_utf8_frames(w.u, a, base, span, descs, flags, n, 1, stream_first, n_streams, carry_in, s);
+
+    const bool temporal = temporal_stores(code);
+    constexpr uint64_t kMaxBlocks = (1ull << 32) / kBlock / 2;
+    // the apply's test for the capped launches and its means (dynamic LDS the
+    // kernel does not use), with this kernel's own number of blocks per CU
+    const unsigned lds_pad = unmask_capped(span, n) ? lds_pad_for(kFusedBlocksPerCu, kFusedStaticLds) : 0u;
+    const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
+    for (uint64_t b0 = 0; b0 < nfull; b0 += kMaxBlocks) {
+        const dim3 grid((uint32_t)(nfull - b0 < kMaxBlocks ? nfull - b0 : kMaxBlocks));
+        const uint32_t bb = (uint32_t)b0;
+        if (lds_pad && !temporal)
+            hipLaunchKernelGGL((unmask_utf8_split_kernel<true, true>), grid, dim3(kBlock), lds_pad, s, base, descs, n,
+                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
+        else if (lds_pad)
+            hipLaunchKernelGGL((unmask_utf8_split_kernel<true, false>), grid, dim3(kBlock), lds_pad, s, base, descs, n,
+                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
+        else if (!temporal)
+            hipLaunchKernelGGL((unmask_utf8_split_kernel<false, true>), grid, dim3(kBlock), 0, s, base, descs, n,
+                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
+        else
+            hipLaunchKernelGGL((unmask_utf8_split_kernel<false, false>), grid, dim3(kBlock), 0, s, base, descs, n,
+                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
+    }
+    if (ntiles > nfull)  // the partial last tile
+        hipLaunchKernelGGL(unmask_utf8_tail_kernel, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, a.map, a.head,
+                           a.views, a.first_bad, edges, (uint32_t)nfull);
+    launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
+    return hip_status(hipGetLastError());
 }
 
 }  // namespace kmws
@@ -442,33 +967,18 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
     if (n && workspace_bytes < w.total) return KMWS_ERR_BUFFER_TOO_SMALL;
     if (!have_device()) return KMWS_ERR_NOT_SUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) {  // nothing to judge: every stream's state passes through
-        if (carry_out && n_streams)
-            hipLaunchKernelGGL(utf8_carry_copy_kernel, dim3((n_streams + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                               n_streams, carry_in, carry_out);
-        return hip_status(hipGetLastError());
-    }
+    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);  // every stream's state passes through
     kmws_status st = launch_plan(span, descs, n, workspace, w.plan_bytes, s);
     if (st != KMWS_OK) return st;
     note_device_batch(span, s);
 
-    uint8_t* wsb = static_cast<uint8_t*>(workspace);
-    WsHead* head = static_cast<WsHead*>(workspace);
-    const TileRec* map = reinterpret_cast<const TileRec*>(head + 1);
-    uint32_t* first_bad = reinterpret_cast<uint32_t*>(wsb + w.first_bad);
-    Utf8Elem* elems = reinterpret_cast<Utf8Elem*>(wsb + w.elems);
-    Utf8Elem* aggs = reinterpret_cast<Utf8Elem*>(wsb + w.aggs);
-    Utf8Elem* pre = reinterpret_cast<Utf8Elem*>(wsb + w.pre);
-    Utf8Elem* carry_tmp = reinterpret_cast<Utf8Elem*>(wsb + w.carry);
-    const Utf8View* views = reinterpret_cast<const Utf8View*>(elems);
-    const uint32_t sblk = stream_first ? (n_streams + 1u + kBlock - 1) / kBlock : 0u;
+    const Utf8Arrays a = utf8_arrays(workspace, w);
+    WsHead* head = a.head;
+    const TileRec* map = a.map;
+    uint32_t* first_bad = a.first_bad;
+    const Utf8View* views = a.views;
     const int masked = payload_masked != 0;
-
-    hipLaunchKernelGGL(utf8_elem_kernel, dim3(w.nblk > sblk ? w.nblk : sblk), dim3(kBlock), 0, s, base, span, descs,
-                       flags, n, masked, stream_first, n_streams, carry_in, elems, first_bad, aggs, w.nblk, head);
-    hipLaunchKernelGGL(utf8_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, aggs, pre, w.nblk);
-    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(w.nblk), dim3(kBlock), 0, s, flags, n, stream_first, n_streams, carry_in,
-                       elems, pre, first_bad, carry_tmp);
+    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, stream_first, n_streams, carry_in, s);
 
     const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;  // launch_plan bounded it
     Split sp;
@@ -484,10 +994,54 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
             hipLaunchKernelGGL(utf8_payload_kernel<false>, grid, dim3(kBlock), 0, s, base, span, descs, n, map, head,
                                views, first_bad, tm, (uint32_t)b0);
     }
-    const uint32_t fin_lanes = carry_out && n_streams > n ? n_streams : n;
-    hipLaunchKernelGGL(utf8_finish_kernel, dim3((fin_lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n,
-                       stream_first, n_streams, views, first_bad, carry_tmp, carry_in, carry_out, out);
+    launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
     return hip_status(hipGetLastError());
+}
+
+size_t kmws_unmask_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams)
+{
+    return fused_ws(span, n, n_streams).total;
+}
+
+kmws_status kmws_unmask_utf8_batch(uint8_t* base, uint64_t span, const kmws_desc* descs, const uint16_t* flags,
+                                   uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                                   const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
+                                   void* workspace, size_t workspace_bytes, int schedule, void* stream)
+{
+    const FusedWs w = fused_ws(span, n, n_streams);
+    uint32_t code = 0;
+    kmws_status st = fused_check(base, base && descs && flags && out && workspace, n, stream_first, n_streams, span,
+                                 schedule, workspace_bytes, w, &code);
+    if (st != KMWS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);
+    st = launch_plan(span, descs, n, workspace, w.u.plan_bytes, s);
+    if (st != KMWS_OK) return st;
+    note_device_batch(2 * span, s);
+    return launch_fused(code, base, span, descs, flags, n, stream_first, n_streams, carry_in, carry_out, out, workspace,
+                        w, s);
+}
+
+kmws_status kmws_unpack_unmask_utf8(uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n, int mode,
+                                    kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                    const uint32_t* stream_first, uint32_t n_streams, const kmws_utf8_carry* carry_in,
+                                    kmws_utf8_carry* carry_out, uint8_t* out_utf8, void* workspace,
+                                    size_t workspace_bytes, int schedule, void* stream)
+{
+    const FusedWs w = fused_ws(wire_len, n, n_streams);
+    uint32_t code = 0;
+    if (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) return KMWS_ERR_INVALID_PARAM;
+    const bool fits = (wire_len + kPlanTile - 1) / kPlanTile <= 0x7FFFFFFFull;  // the plan's tile index
+    kmws_status st = fused_check(wire, wire && hdr_off && out_desc && out_flags && out_utf8 && workspace && fits, n,
+                                 stream_first, n_streams, wire_len, schedule, workspace_bytes, w, &code);
+    if (st != KMWS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);
+    st = launch_unpack_plan(wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err, workspace, s);
+    if (st != KMWS_OK) return st;
+    note_device_batch(2 * wire_len, s);
+    return launch_fused(code, wire, wire_len, out_desc, out_flags, n, stream_first, n_streams, carry_in, carry_out,
+                        out_utf8, workspace, w, s);
 }
 
 }  // extern "C"

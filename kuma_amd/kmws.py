@@ -48,6 +48,7 @@ EXPORTS = [
     "kmws_tx_batch_pending", "kmws_tx_batch_attach_ring", "kmws_host_alloc", "kmws_host_free",
     "kmws_set_device_policy", "kmws_set_thread_device", "kmws_thread_device", "kmws_thread_attach",
     "kmws_utf8_workspace_size", "kmws_utf8_validate",
+    "kmws_unmask_utf8_workspace_size", "kmws_unmask_utf8_batch", "kmws_unpack_unmask_utf8",
 ]
 # per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
 UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
@@ -194,6 +195,9 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_device_numa_node": (i32, [i32, C.POINTER(C.c_int)]),
         "kmws_utf8_workspace_size": (sz, [u64, u32, u32]),
         "kmws_utf8_validate": (i32, [u8p, u64, vp, vp, u32, i32, vp, u32, vp, vp, u8p, vp, sz, vp]),
+        "kmws_unmask_utf8_workspace_size": (sz, [u64, u32, u32]),
+        "kmws_unmask_utf8_batch": (i32, [u8p, u64, vp, vp, u32, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
+        "kmws_unpack_unmask_utf8": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -939,6 +943,73 @@ def unpack_unmask(wire, hdr_off, mode: int, out_desc, out_flags, out_err, ws: Wo
     _check(lib().kmws_unpack_unmask(wire.data_ptr(), wire_len, hdr_off.data_ptr(), n, mode, out_desc.data_ptr(),
                                     _opt(out_flags), _opt(out_err), ws.ptr, ws.nbytes, _sched_arg(ws, schedule),
                                     _stream_handle(stream)), "kmws_unpack_unmask")
+
+
+def unmask_utf8_workspace_size(span: int, n: int, n_streams: int = 1) -> int:
+    return lib().kmws_unmask_utf8_workspace_size(span, n, n_streams)
+
+
+def _check_streams(stream_first, carry_in, carry_out, dev) -> int:
+    ns = 1
+    if stream_first is not None:
+        _check_tensor(stream_first, "stream_first", 4, dev, 2)
+        ns = stream_first.numel() - 1
+    for name, c in (("carry_in", carry_in), ("carry_out", carry_out)):
+        if c is not None:
+            _check_tensor(c, name, 1, dev, 8 * ns)
+    return ns
+
+
+def unmask_utf8(base, descs, flags, out, ws: Workspace, span: Optional[int] = None, stream_first=None,
+                carry_in=None, carry_out=None, schedule: Optional[int] = None, stream=None) -> None:
+    """kmws_unmask_utf8_batch (stream-ordered): the in-place unmask of
+    unmask_batch and the verdicts of utf8_validate(masked=True) in one pass over
+    the payload.  base: still masked, unmasked on return; the other arguments as
+    utf8_validate's; ws: unmask_utf8_workspace_size(span, n, n_streams), with
+    `schedule`, else ws.schedule, else the default.  out and carry_out are valid
+    only when the workspace status is 0 afterwards (nothing is unmasked then)."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(base, "base", 1, dev)
+    _check_tensor(flags, "flags", 2, dev, n)
+    _check_tensor(out, "out", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
+    span = base.numel() if span is None else span
+    if span > base.numel():
+        raise ValueError(f"span {span} exceeds base ({base.numel()} bytes)")
+    _check(lib().kmws_unmask_utf8_batch(base.data_ptr(), span, descs.data_ptr(), flags.data_ptr(), n,
+                                        _opt(stream_first), ns, _opt(carry_in), _opt(carry_out), out.data_ptr(),
+                                        ws.ptr, ws.nbytes, _sched_arg(ws, schedule), _stream_handle(stream)),
+           "kmws_unmask_utf8_batch")
+
+
+def unpack_unmask_utf8(wire, hdr_off, mode: int, out_desc, out_flags, out_err, out_utf8, ws: Workspace,
+                       wire_len: Optional[int] = None, stream_first=None, carry_in=None, carry_out=None,
+                       schedule: Optional[int] = None, stream=None) -> None:
+    """kmws_unpack_unmask_utf8: unpack_unmask with the UTF-8 verdicts of the
+    frames it parses (out_utf8, uint8 (n,)) from the same payload pass; ws:
+    unmask_utf8_workspace_size(wire_len, n, n_streams).  out_flags is required;
+    a header-error frame is judged as the empty frame it becomes: read out_err
+    first."""
+    wire_len = wire.numel() if wire_len is None else wire_len
+    n = hdr_off.shape[0]
+    dev = wire.device
+    _check_tensor(hdr_off, "hdr_off", 8, dev, n)
+    _check_tensor(out_desc, "out_desc", 8, dev, 2 * n)
+    _check_tensor(out_flags, "out_flags", 2, dev, n)
+    if out_err is not None:
+        _check_tensor(out_err, "out_err", 1, dev, n)
+    _check_tensor(out_utf8, "out_utf8", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
+    if wire.numel() < wire_len:
+        raise ValueError("wire shorter than wire_len")
+    _check(lib().kmws_unpack_unmask_utf8(wire.data_ptr(), wire_len, hdr_off.data_ptr(), n, mode, out_desc.data_ptr(),
+                                         out_flags.data_ptr(), _opt(out_err), _opt(stream_first), ns,
+                                         _opt(carry_in), _opt(carry_out), out_utf8.data_ptr(), ws.ptr, ws.nbytes,
+                                         _sched_arg(ws, schedule), _stream_handle(stream)),
+           "kmws_unpack_unmask_utf8")
 
 
 def unpack_gather(wire, hdr_off, mode: int, out_desc, out_flags, out_err, dst, dst_off, ws: Workspace,
