@@ -333,8 +333,10 @@ kmws_status kmws_unmask_apply_sched(uint8_t* base, uint64_t span, const kmws_des
 int kmws_unmask_default_schedule(uint64_t span, uint32_t n);
 
 /* Optional one-time tuning of ONE batch (like a cuDNN benchmark pass): runs
- * every placement kind with both store policies twice on this batch (the XOR
- * applied twice leaves the payload unchanged), times them with events on
+ * every placement kind with both store policies on this batch, two launches
+ * per timing (the XOR applied twice leaves the payload unchanged), in one
+ * warm-up round and two timed rounds, a schedule's time being the lower of its
+ * two; times them with events on
  * `stream` (synchronizes) and returns the fastest schedule code (or a negative
  * status) for the caller to pass to kmws_unmask_apply_sched.  Nothing is
  * recorded: the next batch, on any workspace, gets the default unless its

@@ -50,9 +50,19 @@ __device__ uint32_t g_diag_slots = 0;
         }                                              \
         __builtin_amdgcn_sched_barrier(0);             \
     } while (0)
+#define KMWS_STAMP_AFTER_VM(st, i, cnt)                 \
+    do {                                               \
+        __builtin_amdgcn_sched_barrier(0);             \
+        if (st) {                                      \
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory"); \
+            (st)[i] = __builtin_amdgcn_s_memtime();    \
+        }                                              \
+        __builtin_amdgcn_sched_barrier(0);             \
+    } while (0)
 #else
 #define KMWS_STAMP(st, i) do { (void)(st); } while (0)
 #define KMWS_STAMP_AFTER(st, i, waitcnt) do { (void)(st); } while (0)
+#define KMWS_STAMP_AFTER_VM(st, i, cnt) do { (void)(st); } while (0)
 #endif
 
 // Frame f's records for the tiles [b0, b1) whose start lies in its region, and
@@ -172,7 +182,7 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
     // Two frames at most (a frame boundary inside the tile, e.g. a packed wire
     // image of frames longer than a tile): both descriptors are block-uniform
     // scalars, each word's mask is built from them directly -- no LDS, no
-    // barrier (at 2 blocks per CU a barrier's latency is not hidden; TWO: the
+    // barrier (at 2-3 blocks per CU a barrier's latency is not hidden; TWO: the
     // capped launches; uncapped, the LDS path measured faster on 4 KiB frames).
     // Every mask is built before the first store, so the mask ALU runs while
     // the payload loads are still in flight (built word by word between the
@@ -356,11 +366,54 @@ __global__ void __launch_bounds__(kBlock) unmask_split_kernel(uint8_t* __restric
     }
     __builtin_amdgcn_sched_barrier(0);
     KMWS_STAMP(st, 1);
-    load_tile<V, true>(base, lo, lo + Cfg::kTile, v);
-    __builtin_amdgcn_sched_barrier(0);
-    KMWS_STAMP(st, 2);
-    finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, (status & kStatusBadDesc) == 0, v,
-                                  s_off, s_end, s_key, nullptr, st);
+    if constexpr (kUnmaskDepth < V) {
+        // Staged loads (kUnmaskDepth, kmws_unmask_tile.hpp): the first D words go
+        // out here; a covered tile then runs word by word -- word i is waited
+        // for, load i + D issued, word i stored.  The load goes out ahead of the
+        // store: vmcnt is one in-order queue, so the wait for a load issued
+        // after a store would also wait for that store's acknowledgement.  Any
+        // other tile issues the rest at once and takes finish_tile's paths.  A
+        // bad plan issues no more loads and stores nothing; the D in flight
+        // drain before the wave ends.  The sched_barriers pin load / store
+        // order between the steps; inside the up-front group the compiler is
+        // free (at D = 3 it issues word 1's load ahead of word 0's, so the first
+        // wait covers both: the stream profiles/p04_unmask_depth_ab.txt measured).
+        constexpr int D = kUnmaskDepth;
+        constexpr int SP = NT ? kPolStreamStoreLarge : kPolPlain;
+        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, lo, lo + Cfg::kTile);
+        const bool ok = (status & kStatusBadDesc) == 0;
+        load_tile_words<V>(rs, v, 0, D);
+        __builtin_amdgcn_sched_barrier(0);
+        KMWS_STAMP(st, 2);
+        if (!tile_rec_covered(rec, n)) {
+            load_tile_words<V>(rs, v, D, V);
+            __builtin_amdgcn_sched_barrier(0);
+            finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, ok, v, s_off, s_end, s_key);
+            return;
+        }
+        KMWS_STAMP_AFTER(st, 3, "lgkmcnt(0)");  // the records and the status word are here
+        if (ok) {
+            const uint32_t r = rec.rkey;
+            const uint32_t x0 = 16u * (uint32_t)threadIdx.x;
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                if (i == 0) KMWS_STAMP_AFTER_VM(st, 4, D - 1);  // the first payload word is here
+                const u32x4 w = v[i] ^ r;  // the compiler's wait for word i sits here
+                __builtin_amdgcn_sched_barrier(0);
+                load_tile_words<V>(rs, v, i + D, i + D + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                store_word<SP>(w, rs, x0 + 16u * (uint32_t)(kBlock * i));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            KMWS_STAMP(st, 5);
+        }
+    } else {
+        load_tile<V, true>(base, lo, lo + Cfg::kTile, v);
+        __builtin_amdgcn_sched_barrier(0);
+        KMWS_STAMP(st, 2);
+        finish_tile<V, true, TWO, NT>(base, lo, lo + Cfg::kTile, d, n, rec, rec_next, (status & kStatusBadDesc) == 0,
+                                      v, s_off, s_end, s_key, nullptr, st);
+    }
 #ifdef KMWS_DIAG_PHASE_STAMPS
     const uint32_t blk = b0 + blockIdx.x;
     if (blk % kDiagEvery == 0 && blk / kDiagEvery < g_diag_slots && threadIdx.x == 0 && st[5] != 0)
@@ -481,13 +534,18 @@ __global__ void __launch_bounds__(kBlock) check_unmasked_kernel(const uint8_t* _
     if (bad) atomicAdd(mismatches, bad);
 }
 
-// Blocks of an apply grid resident per CU.  Fewer blocks in flight stream HBM
-// better: 2 blocks of 256 lanes per CU (32 KiB of loads in flight per CU) run
-// the 64 GiB batch at 84.5-84.8 % of peak against 82.4-82.9 % with the 6 the
-// registers allow, 3 blocks at 83.4 %, 1 block at 65-75 %
-// (profiles/r02ag_unmask_occupancy.txt).  The cap is dynamic LDS the kernel does
-// not use: a block asks for just over a third of the CU's LDS.
-constexpr unsigned kUnmaskBlocksPerCu = 2;
+// Blocks of an apply grid resident per CU, chosen together with the load depth
+// kUnmaskDepth (kmws_unmask_tile.hpp) as one pair (blocks, depth).  With every
+// load of a tile issued up front (depth 4) fewer blocks stream HBM better: 2
+// blocks of 256 lanes per CU ran the 64 GiB batch at 84.5-84.8 % of peak against
+// 82.4-82.9 % with the 6 the registers allow, 3 blocks at 83.4 %, 1 block at
+// 65-75 % (profiles/r02ag_unmask_occupancy.txt).  With staged loads the best
+// pairs are (3, 3), (4, 1) and (3, 2): 20.18-20.39 / 20.22-20.36 / 20.27-20.44 ms
+// against 20.59-20.74 for (2, 4), the pair before; (3, 3) is the one that also
+// gains on the packed wire under the default schedule
+// (profiles/p04_unmask_depth_ab.txt).  The cap is dynamic LDS the kernel does
+// not use: a block asks for just over a quarter of the CU's LDS.
+constexpr unsigned kUnmaskBlocksPerCu = 3;
 
 // Dynamic LDS that lets exactly `blocks_per_cu` blocks of `static_lds` bytes of
 // static LDS share a CU (0 if the device cannot be asked).
@@ -747,9 +805,12 @@ kmws_status kmws_unpack_unmask(uint8_t* wire, uint64_t wire_len, const uint64_t*
     return launch_apply(code, wire, wire_len, out_desc, n, workspace, workspace_bytes, s);
 }
 
-// Times each schedule on the caller's batch, twice per schedule (XOR applied
-// twice is the identity, so the payload is unchanged on return), and returns
-// the fastest; nothing is recorded.  Synchronizes.
+// Times each schedule on the caller's batch, two launches per timing (XOR
+// applied twice is the identity, so the payload is unchanged on return): one
+// warm-up round over every schedule, then two timed rounds; a schedule's time
+// is the lower of its two (one round alone let a 0.3 ms outlier pick a slower
+// schedule, profiles/p01_unmask_tilerec_policy_ab.txt section 5).  Returns the
+// fastest; nothing is recorded.  Synchronizes.
 int kmws_unmask_autotune(uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n, void* workspace,
                          size_t workspace_bytes, void* stream)
 {
@@ -767,12 +828,14 @@ int kmws_unmask_autotune(uint8_t* base, uint64_t span, const kmws_desc* descs, u
         (void)hipEventDestroy(e0);
         return KMWS_ERR_FAILED;
     }
-    float best = 1e30f;
-    uint32_t pick = default_schedule(span, n);
-    for (int rep = 0; rep < 2 && st == KMWS_OK; ++rep) {
-        for (uint32_t kind : kinds) {
-            for (uint32_t store : {kSchedNT, kSchedTemporal}) {
-                const uint32_t g = kind | store;
+    constexpr int kKinds = sizeof(kinds) / sizeof(kinds[0]);
+    static const uint32_t stores[2] = {kSchedNT, kSchedTemporal};
+    float t_min[kKinds][2];
+    for (auto& t : t_min) t[0] = t[1] = 1e30f;
+    for (int rep = 0; rep < 3 && st == KMWS_OK; ++rep) {
+        for (int ki = 0; ki < kKinds; ++ki) {
+            for (int si = 0; si < 2; ++si) {
+                const uint32_t g = kinds[ki] | stores[si];
                 if (hipEventRecord(e0, s) != hipSuccess) { st = KMWS_ERR_FAILED; break; }
                 for (int k = 0; k < 2 && st == KMWS_OK; ++k)
                     st = launch_apply(g, base, span, descs, n, workspace, workspace_bytes, s);
@@ -782,10 +845,7 @@ int kmws_unmask_autotune(uint8_t* base, uint64_t span, const kmws_desc* descs, u
                 }
                 float ms = 0;
                 (void)hipEventElapsedTime(&ms, e0, e1);
-                if (rep == 1 && ms < best) {  // rep 0 warms every schedule up
-                    best = ms;
-                    pick = g;
-                }
+                if (rep > 0 && ms < t_min[ki][si]) t_min[ki][si] = ms;  // rep 0 warms every schedule up
             }
             if (st != KMWS_OK) break;
         }
@@ -793,6 +853,14 @@ int kmws_unmask_autotune(uint8_t* base, uint64_t span, const kmws_desc* descs, u
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     if (st != KMWS_OK) return st;
+    float best = 1e30f;
+    uint32_t pick = default_schedule(span, n);
+    for (int ki = 0; ki < kKinds; ++ki)
+        for (int si = 0; si < 2; ++si)
+            if (t_min[ki][si] < best) {
+                best = t_min[ki][si];
+                pick = kinds[ki] | stores[si];
+            }
     return (int)pick;
 }
 

@@ -80,8 +80,31 @@ __device__ __forceinline__ void load_tile(uint8_t* __restrict__ base, uint64_t t
     }
 }
 
+// Words [I0, I1) of a full tile, back to back: the staged apply of the capped
+// launches issues a tile's loads in two parts (kUnmaskDepth).
+template <int V, int POL = kPolStreamLoad>
+__device__ __forceinline__ void load_tile_words(__amdgpu_buffer_rsrc_t rs, u32x4 (&v)[V], int i0, int i1)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < V; ++i)
+        if (i >= i0 && i < i1)
+            v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(16u * (uint32_t)(tid + kBlock * i)), 0, POL);
+}
+
 // Tile geometry used by the product path (tuned on MI355X).
 constexpr int kUnmaskV = 4;
+// Load depth of the capped launches (unmask_split_kernel<V, TWO = true, NT>):
+// the payload loads a lane keeps outstanding.  kUnmaskV: all of a tile's loads
+// go out up front.  Below it, a covered tile issues load i + depth when word i
+// has arrived, ahead of word i's store; the other tile kinds issue the rest at
+// once.  With kUnmaskBlocksPerCu (kmws_unmask.hip) it sets the payload bytes in
+// flight per CU, blocks x depth x 4 KiB, picked as one pair by measurement:
+// (3, 3), 36 KiB, ran the 64 GiB aligned batch at 20.18-20.39 ms against
+// 20.59-20.74 for (2, 4) and 20.62-20.66 for (3, 4)
+// (profiles/p04_unmask_depth_ab.txt).
+constexpr int kUnmaskDepth = 3;
+static_assert(kUnmaskDepth >= 1 && kUnmaskDepth <= kUnmaskV, "1 .. all of a tile's loads");
 using ProdCfg = UnmaskCfg<kUnmaskV>;
 constexpr uint32_t kUnmaskStaticLds = ProdCfg::kCap * (8 + 8 + 4);  // s_off, s_end, s_key
 

@@ -6,7 +6,9 @@ through kuma_amd/build.py `defines`; never kmws.lib(), never a product
 variant), runs the headline shape -- 64 KiB frames in an aligned arena, the
 default schedule -- and reads the six s_memtime stamps one block in 1024
 kept: entry, index math done, payload loads issued, metadata arrived, first
-payload word arrived, last store issued.  Prints the median share of each
+payload word arrived, last store issued (with staged loads, kUnmaskDepth below
+4: the up-front loads issued, and the store phase holds the later loads and
+the waits for the later words).  Prints the median share of each
 phase of the block's entry-to-last-store time, in shader cycles.  Stamping
 costs about a tenth of the wave's cycles, so this is a record of shares.
 

@@ -5,15 +5,22 @@
 // interleaved in one process over one allocation filled with random bytes.
 // Stand-alone (no library): tools/membw_probe.hip's other modes need product
 // entry points that no longer exist.
+// `depth` mode: the same stream with the product's policies (nt loads, nt sc1
+// stores) over pairs (B, D) -- B blocks resident per CU, D payload loads
+// outstanding per lane: word i is waited for, load i + D issued, word i stored
+// (D = 4: all loads up front, the policy mode's kernel) -- B x D x 4 KiB of
+// payload in flight per CU.
 //
 // build: hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 tools/policy_probe.hip -o tools/policy_probe
 // run:   tools/policy_probe [GiB = 64] [reps = 5]
+//        tools/policy_probe depth [GiB = 64] [reps = 5]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -60,6 +67,77 @@ __global__ void __launch_bounds__(kB) xor_split4(uint8_t* base, uint32_t c)
         __builtin_amdgcn_raw_buffer_store_b128(v[i] ^ c, rs, (int)(16u * (threadIdx.x + kB * i)), 0, SP);
 }
 
+// D loads outstanding per lane; the next load goes out ahead of the store (vmcnt
+// is one in-order queue: a load issued behind a store waits for that store too)
+template <int D>
+__global__ void __launch_bounds__(kB) xor_split4_depth(uint8_t* base, uint32_t c)
+{
+    constexpr int LP = 2, SP = 18;  // nt loads, nt sc1 stores
+    const uint32_t q = gridDim.x >> 2;
+    const uint64_t tile = (uint64_t)(blockIdx.x & 3u) * q + (blockIdx.x >> 2);
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(base + tile * kTile, (short)0, (int)kTile, 0x00020000);
+    u32x4 v[kV];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+        v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(16u * (threadIdx.x + kB * i)), 0, LP);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < kV; ++i) {
+        const u32x4 w = v[i] ^ c;
+        __builtin_amdgcn_sched_barrier(0);
+        if (i + D < kV)
+            v[i + D] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(16u * (threadIdx.x + kB * (i + D))), 0, LP);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(16u * (threadIdx.x + kB * i)), 0, SP);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+static void launch_depth(int d, uint8_t* buf, uint32_t grid, unsigned pad)
+{
+    switch (d) {
+    case 1: hipLaunchKernelGGL(xor_split4_depth<1>, dim3(grid), dim3(kB), pad, 0, buf, 0x5a5a5a5au); break;
+    case 2: hipLaunchKernelGGL(xor_split4_depth<2>, dim3(grid), dim3(kB), pad, 0, buf, 0x5a5a5a5au); break;
+    case 3: hipLaunchKernelGGL(xor_split4_depth<3>, dim3(grid), dim3(kB), pad, 0, buf, 0x5a5a5a5au); break;
+    default: hipLaunchKernelGGL(xor_split4_depth<4>, dim3(grid), dim3(kB), pad, 0, buf, 0x5a5a5a5au); break;
+    }
+}
+
+// (blocks per CU, loads outstanding per lane), interleaved like the policies
+static int depth_mode(uint8_t* buf, uint64_t bytes, uint32_t tiles, int lds, int reps)
+{
+    static const int kPairs[][2] = {{2, 4}, {2, 3}, {3, 2}, {6, 1}, {5, 1}, {7, 1}, {4, 2}, {8, 1}, {3, 3}, {5, 2}};
+    constexpr int kN = sizeof(kPairs) / sizeof(kPairs[0]);
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    std::vector<float> ms[kN];
+    for (int r = 0; r < reps + 1; ++r)
+        for (int p = 0; p < kN; ++p) {
+            const unsigned pad = (unsigned)lds / (kPairs[p][0] + 1) + 1;  // one more block does not fit
+            CK(hipEventRecord(e0, 0));
+            launch_depth(kPairs[p][1], buf, tiles, pad);
+            CK(hipEventRecord(e1, 0));
+            CK(hipEventSynchronize(e1));
+            CK(hipGetLastError());
+            float t = 0;
+            CK(hipEventElapsedTime(&t, e0, e1));
+            if (r > 0) ms[p].push_back(t);  // round 0 warms up
+        }
+    printf("split-4 in-place XOR, %.1f GiB, random fill, nt loads, nt sc1 stores, %d reps; share of 8 TB/s\n",
+           bytes / 1073741824.0, reps);
+    for (int p = 0; p < kN; ++p) {
+        std::vector<float> v = ms[p];
+        std::sort(v.begin(), v.end());
+        const double med = v[v.size() / 2];
+        printf("blocks/CU %d depth %d (%2d KiB/CU) median %8.3f ms  best %8.3f  worst %8.3f  -> %.4f\n", kPairs[p][0],
+               kPairs[p][1], 4 * kPairs[p][0] * kPairs[p][1], med, v.front(), v.back(),
+               2.0 * bytes / (med * 1e-3) / 8e12);
+    }
+    return 0;
+}
+
 template <int L, int S>
 static void launch(uint8_t* buf, uint32_t grid, unsigned pad)
 {
@@ -91,6 +169,8 @@ static void launch_ls(int l, int s, uint8_t* buf, uint32_t grid, unsigned pad)
 
 int main(int argc, char** argv)
 {
+    const bool depth = argc > 1 && strcmp(argv[1], "depth") == 0;
+    if (depth) --argc, ++argv;
     const uint64_t bytes = (argc > 1 ? strtoull(argv[1], 0, 0) : 64ull) << 30;
     const int reps = argc > 2 ? atoi(argv[2]) : 5;
     const uint64_t tiles = bytes / kTile;
@@ -104,6 +184,7 @@ int main(int argc, char** argv)
     CK(hipDeviceSynchronize());
     int lds = 0;
     CK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, 0));
+    if (depth) return depth_mode(buf, bytes, (uint32_t)tiles, lds, reps);
     const unsigned pad = (unsigned)lds / 3 + 1;  // a third block does not fit: 2 per CU
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
