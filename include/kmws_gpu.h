@@ -108,7 +108,9 @@ enum kmws_opcode { KMWS_OP_CONTINUE = 0, KMWS_OP_TEXT = 1, KMWS_OP_BINARY = 2,
 #define KMWS_MAX_HEADER_SIZE 14         /* WS_MAX_HEADER_SIZE, wsdefs.h:37 */
 #define KMWS_MAX_FRAME_DATA_LENGTH (10u * 1024u * 1024u)  /* WSHandler.cpp:110 */
 
-/* FrameHeader (wsdefs.h:74-88) with the bitfields widened to bytes. */
+/* FrameHeader (wsdefs.h:74-88) with the bitfields widened to bytes.  `reserved`
+ * is 0, except during the frame callback of a decoder with the UTF-8 check on
+ * (kmws_decoder_set_utf8_check): then it holds the frame's KMWS_UTF8_* value. */
 typedef struct kmws_frame_hdr {
     uint8_t  fin, rsv1, rsv2, rsv3, opcode, mask, plen, reserved;
     uint64_t xpl64;                      /* union xpl: xpl16 = low 16 bits */
@@ -176,6 +178,45 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
  * frame callback only sees the view (WSHandler.cpp:285).  Pinned chunks are
  * always unmasked in place (zero-copy). */
 void kmws_decoder_set_in_place(kmws_decoder* dec, int on);
+
+/* Opt-in UTF-8 check of text messages on the host path (RFC 6455 5.6 / 8.1),
+ * off by default; NULL is a no-op.  With it on, kmws_decoder_feed and
+ * kmws_decoder_feed_deferred / kmws_rx_batch_* (so RxLoop too) deliver every
+ * frame with a KMWS_UTF8_* value (defined below, with their exact meaning, at
+ * kmws_utf8_validate) in kmws_frame_hdr.reserved while its callback runs --
+ * kmws_frame_utf8(hdr) reads it.  With the check off the byte is 0
+ * (== KMWS_UTF8_NOT_TEXT), as it always was.  Per connection the values are
+ * exactly kmws_utf8_validate's for one stream, the stream being everything this
+ * decoder was fed since it was created or kmws_decoder_reset: OK / BAD /
+ * AFTER_BAD / NOT_TEXT as defined there, including rule (b) -- a FIN that ends
+ * inside a code point, which an empty frame can do.  The message state lives in
+ * the decoder, survives across feeds and across rx generations in flight, and
+ * is cleared by kmws_decoder_reset.  The verdict is advisory: every frame is
+ * unmasked and delivered as without the check and the feeds' return values do
+ * not change; the application closes with 1007 when it sees KMWS_UTF8_BAD.
+ * Switch only between messages and while none of the decoder's frames are
+ * pending in a batch.
+ *
+ * How: the host parser, which walks each connection's frames in order anyway,
+ * keeps the message state (a few instructions per frame); the payload bytes
+ * are checked by the GPU in the pass that unmasks them.  Unmasked frames of a
+ * CLIENT-mode decoder, which otherwise need no GPU work, are sent through that
+ * pass for the check alone (nothing is stored to them); empty frames never need
+ * the GPU.  Cost: a call or generation that holds a checked frame (a text
+ * message's frame with payload) is not posted to the resident worker -- the
+ * resident grid does not know the rule yet -- but launched, so with the check
+ * on text traffic gives up the launch-free path; binary and control-only
+ * generations, and everything with the check off, go exactly as before.  If
+ * the GPU step of a call or generation fails, its frames are dropped as
+ * without the check, and the message that was open across them is no longer
+ * checkable: its later frames report KMWS_UTF8_NOT_TEXT until the next message
+ * head.  Not done: the reason text of a CLOSE frame (at most 123 bytes: the
+ * host checks it) and the byte offset of the error. */
+void kmws_decoder_set_utf8_check(kmws_decoder* dec, int on);
+/* The KMWS_UTF8_* value of a frame, valid during its frame callback.  Also
+ * exported as a function for callers that cannot use a macro. */
+uint8_t kmws_frame_utf8(const kmws_frame_hdr* hdr);
+#define kmws_frame_utf8(h) ((h)->reserved)
 
 /* WSHandler::handleDataMask(key, KMBuffer&) (WSHandler.cpp:312-322) and, with
  * nseg == 1, handleDataMask(key, data, len) (:303-310) for HOST buffers: the
@@ -527,9 +568,12 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  * which an empty FIN frame can do.
  *
  * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
- * checks it); the byte offset of the error; kmws_decoder_feed / RxLoop and the
- * resident grid do not call this yet; the gather form (kmws_unpack_gather) has
- * no fused validation (the in-place unmask has: kmws_unmask_utf8_batch below). */
+ * checks it); the byte offset of the error; the resident grid does not know the
+ * rule (the host path has the check through kmws_decoder_set_utf8_check, and
+ * launches the generations that hold a checked frame instead of posting them
+ * to the grid); the gather form
+ * (kmws_unpack_gather) has no fused validation (the in-place unmask has:
+ * kmws_unmask_utf8_batch below). */
 kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
                                const uint16_t* flags, uint32_t n, int payload_masked,
                                const uint32_t* stream_first, uint32_t n_streams,

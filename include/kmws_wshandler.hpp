@@ -712,6 +712,21 @@ public:
         if (st_->dec) kmws_decoder_set_in_place(st_->dec, on ? 1 : 0);
     }
 
+    // kmws_decoder_set_utf8_check: text messages are checked for well-formed
+    // UTF-8 (RFC 6455 5.6 / 8.1) in the GPU pass that unmasks them, with and
+    // without an RxLoop.  Off by default; switch only between messages and
+    // while none of this handler's frames are queued.  Advisory: every frame is
+    // delivered as before; the application closes with 1007 when
+    // lastFrameUtf8() == KMWS_UTF8_BAD.  With it on, generations that hold text
+    // launch instead of running on the resident worker (include/kmws_gpu.h).
+    void setUtf8Check(bool on)
+    {
+        if (st_->dec) kmws_decoder_set_utf8_check(st_->dec, on ? 1 : 0);
+    }
+    // The KMWS_UTF8_* value of the frame being delivered: valid during the
+    // frame callback (kuma's FrameHeader has no spare field to carry it).
+    int lastFrameUtf8() const { return st_->last_utf8; }
+
     void setFrameCallback(FrameCallback cb) { st_->cb = std::move(cb); }  // WSHandler.h:46
 
     void reset()  // WSHandler.cpp:324-327
@@ -813,6 +828,7 @@ private:
             std::memcpy(h.maskey, k->maskey, KMWS_MASK_KEY_SIZE);
             h.length = k->length;
             Buffer view(static_cast<void*>(payload), len, len);
+            s->last_utf8 = kmws_frame_utf8(k);
             if (s->cb) {
                 FrameCallback cb = s->cb;  // the callback may replace or drop itself
                 (void)cb(h, view);
@@ -825,6 +841,7 @@ private:
         WSMode mode = WSMode::CLIENT;
         bool alive = true;
         int last_status = KMWS_OK;
+        int last_utf8 = KMWS_UTF8_NOT_TEXT;  // kmws_frame_hdr.reserved of the frame being delivered
         RxLoop* rx = nullptr;
     };
     std::shared_ptr<State> st_;

@@ -200,6 +200,25 @@ inline uint64_t piece_count(uint64_t off, uint32_t len)
 kmws_status launch_unmask_pieces(uint8_t* base, const kmws_desc* descs, const PieceRec* pieces, uint32_t np,
                                  hipStream_t s);
 
+// The same launch with the UTF-8 check of kmws_decoder_set_utf8_check in its
+// payload pass (kmws_utf8.hip: unmask_pieces_utf8_kernel).  views[f] belongs to
+// descs[f]: w = the look-back at the frame's first payload byte | kUtf8Checked
+// (0: not checked, the frame is only unmasked), slot = the index of the frame's
+// byte in verdict[], which the caller zeroed and reads after the launch has
+// finished: 1 = the rule rejects a byte of the frame.  A descriptor with key 0
+// stores nothing to its payload (the check-only job of an unmasked frame).
+// edge: the four bytes before the piece's first word as they lie in memory
+// before the launch (still masked), read by the host -- another block may
+// already have unmasked them when this piece's block runs; piece 0 has none.
+struct Utf8View;
+struct PieceRecEdge {
+    uint32_t frame;
+    uint32_t piece;
+    uint32_t edge;
+};
+kmws_status launch_unmask_pieces_utf8(uint8_t* base, const kmws_desc* descs, const Utf8View* views,
+                                      const PieceRecEdge* pieces, uint32_t np, uint8_t* verdict, hipStream_t s);
+
 // KMWS_DEVICE_AUTO -> the calling thread's device (kmws_devmap.cpp; negative
 // without a gfx950 device); any other value unchanged.
 int resolve_device(int device);

@@ -12,6 +12,10 @@
 //                               per event-loop iteration), callbacks at flush.
 // There is no CPU unmask path: without a usable gfx950 device a masked frame
 // fails the call with KMWS_ERR_NOT_SUPPORTED.
+// kmws_decoder_set_utf8_check (opt-in): the parser keeps each connection's
+// UTF-8 message state (kmws_utf8_stream.hpp), the payload pass validates the
+// bytes of checked frames while it unmasks them, and the verdict is delivered
+// in kmws_frame_hdr.reserved.  With the check off nothing here changes.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -24,6 +28,7 @@
 
 #include "kmws_gpu.h"
 #include "kmws_host_util.hpp"
+#include "kmws_utf8_stream.hpp"
 
 using namespace kmws;
 
@@ -50,7 +55,17 @@ struct Pending {
     size_t stage_off;   // staged kinds: payload offset in the staging area
     size_t hold_idx;    // kHeld: index into the held buffers
     Origin where;
+    Utf8StreamView uv;  // kmws_decoder_set_utf8_check: the frame's view (w == 0: not checked)
+    uint32_t slot;      // its verdict byte in the stage (kNoSlot: empty or unchecked, no device work)
 };
+
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+
+uint32_t op_byte_of(const kmws_frame_hdr& h)
+{
+    return (uint32_t)((h.fin ? 0x80 : 0) | (h.rsv1 ? 0x40 : 0) | (h.rsv2 ? 0x20 : 0) | (h.rsv3 ? 0x10 : 0) |
+                      (h.opcode & 0x0F));
+}
 
 }  // namespace
 
@@ -72,6 +87,25 @@ struct kmws_decoder {
     std::vector<Pending> pending;
     std::vector<std::vector<uint8_t>> held;
     std::vector<kmws_desc> chunk_descs;
+    // kmws_decoder_set_utf8_check.  The stream's message state, both halves
+    // (kmws_utf8_stream.hpp): the parse-time half advances in the feeds' sinks,
+    // the delivery-time half (which message was reported BAD) when verdicts are
+    // made -- by the synchronous feed before its first callback, by
+    // kmws_rx_batch_poll per generation before that generation's first callback
+    // and only for items that are still live.
+    bool utf8_check = false;
+    Utf8Stream utf8;
+    std::vector<Utf8View> chunk_views;  // one per chunk_descs entry while the check is on
+
+    // Parse-time half for a completed frame whose payload lies contiguous (and
+    // still masked) at `payload`.
+    Utf8StreamView utf8_parse(const kmws_frame_hdr& h, const uint8_t* payload, uint32_t key)
+    {
+        if (!utf8_check) return Utf8StreamView{};
+        uint32_t nb = 0;
+        const uint32_t tail = utf8_stream_tail(payload, h.length, h.mask ? key : 0u, &nb);
+        return utf8_stream_frame(utf8, op_byte_of(h), tail, nb);
+    }
 
     void reset_ctx()  // DecodeContext::reset, WSHandler.h:66-72 (capacity kept)
     {
@@ -89,13 +123,27 @@ constexpr int kWarmStages = 4;
 struct kmws_rx_batch {
     BatchStream bstream;  // first: destroyed after every stage that uses it
     struct Item {
-        kmws_decoder* dec;  // identity only; never dereferenced at delivery
+        // Identity, and with the UTF-8 check the home of the connection's
+        // delivery-time state (Utf8Stream::bad_msg / dropped_msg).  A callback
+        // may destroy a decoder, so it is dereferenced in one place only:
+        // rx_verdicts / rx_drop_utf8, which run when no callback of the
+        // generation has run yet (or none ever will) and touch only items
+        // that are still `live` and checked.  That is safe because a decoder may
+        // be destroyed only after its frames were delivered or after
+        // kmws_rx_batch_discard (the "destroyed" return discards too), and both
+        // clear `live` on every item of it -- in the generation being fed, in
+        // every generation in flight and in the one being delivered -- before
+        // the decoder can be gone.  After kmws_rx_batch_discard the decoder's
+        // state is therefore never read or written again through the batch.
+        kmws_decoder* dec;
         kmws_frame_cb cb;
         void* user;
         kmws_frame_hdr hdr;
         size_t off;       // payload offset in the generation's staging area (direct == nullptr)
         uint8_t* direct;  // payload in the attached ring (no copy)
         bool live;        // false once discarded
+        Utf8StreamView uv;  // the frame's view from the parse-time half (w == 0: not checked)
+        uint32_t slot;      // its verdict byte in the generation's stage (kNoSlot: none)
     };
     // One submitted generation: its frames, and the pinned stage that holds
     // their staged payloads and the unmask launch in flight.
@@ -107,6 +155,7 @@ struct kmws_rx_batch {
     std::vector<Item> items;
     uint64_t pending_bytes = 0;  // masked payload bytes of `items`
     std::vector<kmws_desc> ring_descs;
+    std::vector<Utf8View> ring_views;    // empty: no ring descriptor is checked; else one per descriptor so far
     std::deque<Gen> inflight;            // submitted, not yet delivered (submit order)
     std::vector<std::unique_ptr<PinnedStage>> spare;
     std::vector<Item>* delivering = nullptr;  // the generation whose callbacks are running
@@ -434,8 +483,22 @@ void kmws_decoder_set_mode(kmws_decoder* dec, int mode)
 
 void kmws_decoder_reset(kmws_decoder* dec)
 {
-    if (dec) dec->reset_ctx();
+    if (!dec) return;
+    dec->reset_ctx();
+    utf8_stream_reset(dec->utf8);  // between messages again
 }
+
+void kmws_decoder_set_utf8_check(kmws_decoder* dec, int on)
+{
+    if (!dec) return;
+    const bool want = on != 0;
+    if (want != dec->utf8_check) utf8_stream_reset(dec->utf8);  // switched between messages: nothing is open
+    dec->utf8_check = want;
+}
+
+// kmws_frame_utf8 as a function, for callers that cannot use the macro (FFI).
+#undef kmws_frame_utf8
+uint8_t kmws_frame_utf8(const kmws_frame_hdr* h) { return h ? h->reserved : (uint8_t)KMWS_UTF8_NOT_TEXT; }
 
 void kmws_decoder_set_in_place(kmws_decoder* dec, int on)
 {
@@ -455,6 +518,7 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
     dec->pending.clear();
     dec->held.clear();
     dec->chunk_descs.clear();
+    dec->chunk_views.clear();
     BorrowedStage bs(dec->device);  // given back when the call returns (the decoder may be gone by then)
     int chunk_pinned = -1;  // resolved at the first masked in-chunk frame
     uint8_t* chunk_dv = nullptr;
@@ -466,11 +530,26 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
         const bool masked = h.mask && h.length;  // handleDataMask is a no-op otherwise (:293, :305)
         uint32_t key;
         std::memcpy(&key, h.maskey, 4);
-        if (masked && !bs.get()) return bs.st;
+        // UTF-8 check: the parse-time half.  A checked frame with payload goes
+        // to the GPU whether it is masked or not (key 0: checked, not stored);
+        // an empty one needs no device work (rule (b) is decided here).
+        q.uv = dec->utf8_parse(h, payload, key);
+        q.slot = kNoSlot;
+        const bool checked = (q.uv.w & kUtf8Checked) != 0u && h.length;
+        const bool gpu = masked || checked;
+        const uint32_t dkey = masked ? key : 0u;
+        dec->pending.push_back(q);  // from here on the frame counts as parsed: a failure below drops it
+        Pending& qq = dec->pending.back();
+        if (gpu && !bs.get()) return bs.st;
+        if (checked) qq.slot = bs.s->utf8_slot();
+        auto stage_desc = [&](size_t off) {
+            if (checked) bs.s->add_desc_utf8(off, h.length, dkey, qq.uv.w, qq.slot);
+            else bs.s->add_desc(off, h.length, dkey);
+        };
         if (!reasm) {
-            q.data_ptr = payload;
-            if (!masked) {
-                q.where = kInChunk;
+            qq.data_ptr = payload;
+            if (!gpu) {
+                qq.where = kInChunk;
             } else {
                 if (chunk_pinned < 0) {
                     chunk_dv = chunk_base == dec->last_pageable ? nullptr
@@ -479,44 +558,66 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
                     if (!chunk_pinned) dec->last_pageable = chunk_base;
                 }
                 if (chunk_pinned) {
-                    dec->chunk_descs.push_back(kmws_desc{(uint64_t)(payload - chunk_base), h.length, key});
-                    q.where = kInChunkPinned;
+                    dec->chunk_descs.push_back(kmws_desc{(uint64_t)(payload - chunk_base), h.length, dkey});
+                    if (dec->utf8_check)
+                        dec->chunk_views.push_back(checked ? Utf8View{qq.slot, (qq.uv.w & 0xFFFFFFu) | kUtf8Checked}
+                                                           : Utf8View{0u, 0u});
+                    qq.where = masked ? kInChunkPinned : kInChunk;
                 } else {
                     kmws_status st = bs.s->reserve(h.length);
                     if (st != KMWS_OK) return st;
-                    q.stage_off = bs.s->append(payload, h.length);
-                    bs.s->add_desc(q.stage_off, h.length, key);
-                    q.where = kInChunkStaged;
+                    qq.stage_off = bs.s->append(payload, h.length);
+                    stage_desc(qq.stage_off);
+                    // an unmasked checked frame is staged for the check only: the view stays on the chunk
+                    qq.where = masked ? kInChunkStaged : kInChunk;
                 }
             }
-        } else if (masked) {
+        } else if (gpu) {
             kmws_status st = bs.s->reserve(h.length);
             if (st != KMWS_OK) return st;
-            q.stage_off = bs.s->append(payload, h.length);
-            bs.s->add_desc(q.stage_off, h.length, key);
-            q.where = kStagedMasked;
+            qq.stage_off = bs.s->append(payload, h.length);
+            stage_desc(qq.stage_off);
+            qq.where = kStagedMasked;
         } else {
             dec->held.emplace_back();
             dec->held.back().swap(*reasm);
-            q.hold_idx = dec->held.size() - 1;
-            q.where = kHeld;
+            qq.hold_idx = dec->held.size() - 1;
+            qq.where = kHeld;
         }
-        dec->pending.push_back(q);
         return KMWS_OK;
     };
 
+    // The frames parsed by a call that fails are never delivered, but the
+    // parse-time half has advanced past them: their open message is no longer
+    // checkable until the next message head (utf8_stream_drop).
+    auto drop_utf8 = [&] {
+        for (const Pending& q : dec->pending) utf8_stream_drop(dec->utf8, q.uv);
+    };
+
     const int result = parse_chunk(dec, data, len, sink);
-    if (result < 0) return result;
+    if (result < 0) {
+        drop_utf8();
+        return result;
+    }
 
     // ---- GPU unmask of every masked payload of this call ----
     if (bs.s && (bs.s->n_desc() || !dec->chunk_descs.empty())) {
         const uint64_t chunk_span = (uint64_t)((data + len) - chunk_base);
-        kmws_status st = bs.s->run(chunk_base, chunk_span, &dec->chunk_descs, chunk_dv);
-        if (st != KMWS_OK) return st;
+        kmws_status st = bs.s->run(chunk_base, chunk_span, &dec->chunk_descs, chunk_dv,
+                                   dec->chunk_views.empty() ? nullptr : &dec->chunk_views);
+        if (st != KMWS_OK) {
+            drop_utf8();
+            return st;
+        }
     }
 
     // ---- in-order delivery ----
     const bool in_place = dec->in_place;  // the callbacks may destroy the decoder
+    // the delivery-time half of the UTF-8 check, for the whole call, while the
+    // decoder is certainly alive: hdr.reserved holds the verdict during the callback
+    if (dec->utf8_check)
+        for (Pending& q : dec->pending)
+            q.hdr.reserved = (uint8_t)utf8_stream_verdict(dec->utf8, q.uv, q.slot != kNoSlot && bs.s->utf8_bad(q.slot));
     std::vector<Pending> todo;
     todo.swap(dec->pending);
     std::vector<std::vector<uint8_t>> held;
@@ -899,20 +1000,64 @@ int kmws_decoder_feed_deferred(kmws_decoder* dec, kmws_rx_batch* b, const uint8_
         std::memcpy(&key, h.maskey, 4);
         const bool masked = h.mask && h.length;
         if (masked) b->pending_bytes += h.length;
+        // UTF-8 check: the parse-time half; a checked frame with payload gets a
+        // descriptor (key 0 when unmasked: checked, not stored) and a verdict byte
+        const Utf8StreamView uv = dec->utf8_parse(h, payload, key);
+        const bool checked = (uv.w & kUtf8Checked) != 0u && h.length;
+        uint32_t slot = kNoSlot;
+        const uint32_t dkey = masked ? key : 0u;
         if (!reasm && b->ring && payload >= b->ring && payload + h.length <= b->ring + b->ring_bytes) {
             // payload lies in the caller's pinned ring: unmasked there, no copy
-            if (masked) b->ring_descs.push_back(kmws_desc{(uint64_t)(payload - b->ring), h.length, key});
-            b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, 0, payload, true});
+            if (masked || checked) {
+                if (checked) {
+                    slot = b->stage->utf8_slot();
+                    b->ring_views.resize(b->ring_descs.size(), Utf8View{0u, 0u});
+                    b->ring_views.push_back(Utf8View{slot, (uv.w & 0xFFFFFFu) | kUtf8Checked});
+                }
+                b->ring_descs.push_back(kmws_desc{(uint64_t)(payload - b->ring), h.length, dkey});
+            }
+            b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, 0, payload, true, uv, slot});
             return KMWS_OK;
         }
+        // queued first: a frame the parse-time half has seen must be dropped
+        // through rx_drop_utf8 if its payload cannot be staged
+        b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, 0, nullptr, true, uv, slot});
         kmws_status st = b->stage->reserve(h.length);
-        if (st != KMWS_OK) return st;
+        if (st != KMWS_OK) {
+            utf8_stream_drop(dec->utf8, uv);
+            b->items.pop_back();
+            return st;
+        }
         const size_t off = b->stage->append(payload, h.length);
-        if (masked) b->stage->add_desc(off, h.length, key);
-        b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, off, nullptr, true});
+        b->items.back().off = off;
+        if (checked) {
+            slot = b->stage->utf8_slot();
+            b->items.back().slot = slot;
+            b->stage->add_desc_utf8(off, h.length, dkey, uv.w, slot);
+        } else if (masked) b->stage->add_desc(off, h.length, key);
         return KMWS_OK;
     };
     return parse_chunk(dec, const_cast<uint8_t*>(data), len, sink);
+}
+
+// The frames of a generation that will never be delivered (its launch failed):
+// the parse-time half of their decoders has advanced past them, so their open
+// messages are no longer checkable until the next message head.  Live items
+// only: a discarded item's decoder may be gone (see Item::dec).
+static void rx_drop_utf8(std::vector<kmws_rx_batch::Item>& items)
+{
+    for (auto& it : items)
+        if (it.live && (it.uv.w & kUtf8Checked)) utf8_stream_drop(it.dec->utf8, it.uv);
+}
+
+// The delivery-time half for a whole generation, before its first callback:
+// hdr.reserved holds the verdict while the frame's callback runs.
+static void rx_verdicts(std::vector<kmws_rx_batch::Item>& items, const PinnedStage& stage)
+{
+    for (auto& it : items)
+        if (it.live && (it.uv.w & kUtf8Checked))
+            it.hdr.reserved =
+                (uint8_t)utf8_stream_verdict(it.dec->utf8, it.uv, it.slot != kNoSlot && stage.utf8_bad(it.slot));
 }
 
 kmws_status kmws_rx_batch_attach_ring(kmws_rx_batch* b, uint8_t* ring, size_t bytes)
@@ -954,12 +1099,17 @@ static int rx_submit(kmws_rx_batch* b, bool sync)
     if (b->items.empty()) return 0;
     std::unique_ptr<PinnedStage> next = b->take_stage();
     if (!next) return KMWS_ERR_FAILED;
-    kmws_status st = sync ? b->stage->run(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv)
-                          : b->stage->launch(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv);
+    // a generation with a checked frame launches the pieces kernel with the
+    // check (never the resident worker); any other goes as it always went
+    const std::vector<Utf8View>* rv = b->ring_views.empty() ? nullptr : &b->ring_views;
+    kmws_status st = sync ? b->stage->run(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv, rv)
+                          : b->stage->launch(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv, kResMaxBytesAsync, rv);
     b->ring_descs.clear();
+    b->ring_views.clear();
     b->pending_bytes = 0;
     if (st != KMWS_OK) {
         // nothing of this generation can be delivered masked: drop it
+        rx_drop_utf8(b->items);
         b->items.clear();
         b->stage->clear();
         b->spare.push_back(std::move(next));
@@ -992,10 +1142,12 @@ int kmws_rx_batch_poll(kmws_rx_batch* b, int wait)
         b->inflight.pop_front();
         if (st != KMWS_OK) {  // the launch failed: these payloads are still masked, never delivered
             err = st;
+            rx_drop_utf8(items);
             stage->clear();
             b->spare.push_back(std::move(stage));
             continue;
         }
+        rx_verdicts(items, *stage);  // before the first callback: every live item's decoder is alive
         b->flushing = true;
         b->delivering = &items;
         for (auto& it : items) {

@@ -11,6 +11,7 @@
 
 #include "kmws_common.hpp"
 #include "kmws_gpu.h"
+#include "kmws_utf8_rule.hpp"
 
 namespace kmws {
 
@@ -63,6 +64,13 @@ inline size_t grow(size_t need, size_t have)
 // batch of descriptors can target another pinned buffer (a caller's registered
 // receive or send ring).  The asynchronous rx / tx batches keep one stage per
 // generation in flight (kmws_decoder.cpp).
+// UTF-8 check (kmws_decoder_set_utf8_check): a descriptor added with
+// add_desc_utf8, or an extra one whose view is checked, makes the job a checked
+// one: it is never posted to the resident worker (the grid does not know the
+// rule) and launches unmask_pieces_utf8_kernel instead, with a view per
+// descriptor, the host-read edge word per piece and one verdict byte per
+// checked frame (utf8_slot / utf8_bad), all in the stage's pinned arrays.  A
+// job without a checked frame goes exactly the way it went before.
 // A stream a batch owns and its stages share; declared first in the batch so
 // it is destroyed after every stage.
 struct BatchStream {
@@ -158,11 +166,25 @@ public:
     }
     uint8_t* data() { return h_; }
     void add_desc(uint64_t off, uint32_t len, uint32_t key) { descs_.push_back(kmws_desc{off, len, key}); }
+    // A checked frame's payload: lookback = the 24 bits before its first byte,
+    // slot = its verdict byte (utf8_slot()).  key 0: checked only, not stored.
+    void add_desc_utf8(uint64_t off, uint32_t len, uint32_t key, uint32_t lookback, uint32_t slot)
+    {
+        views_.resize(descs_.size(), Utf8View{0u, 0u});
+        descs_.push_back(kmws_desc{off, len, key});
+        views_.push_back(Utf8View{slot, (lookback & 0xFFFFFFu) | kUtf8Checked});
+    }
+    // The next verdict byte of this job: one per checked, non-empty frame, staged or extra.
+    uint32_t utf8_slot() { return n_slots_++; }
+    // After wait(): the payload pass found a byte of the slot's frame that the rule rejects.
+    bool utf8_bad(uint32_t slot) const { return h_verdict_ && slot < n_slots_ && slot < desc_cap_ && h_verdict_[slot] != 0; }
     size_t n_desc() const { return descs_.size(); }
     void clear()
     {
         len_ = 0;
         descs_.clear();
+        views_.clear();
+        n_slots_ = 0;
     }
 
     // Unmask every staged descriptor (and `extra` over `extra_base`, a pinned
@@ -170,9 +192,10 @@ public:
     // wait().  extra_dv: the device view of extra_base if the caller has it (a
     // ring attached once); else it is looked up here (hipPointerGetAttributes).
     kmws_status run(uint8_t* extra_base = nullptr, uint64_t extra_span = 0,
-                    const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr)
+                    const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr,
+                    const std::vector<Utf8View>* extra_views = nullptr)
     {
-        kmws_status st = launch(extra_base, extra_span, extra, extra_dv, kResMaxBytes);
+        kmws_status st = launch(extra_base, extra_span, extra, extra_dv, kResMaxBytes, extra_views);
         if (st != KMWS_OK) return st;
         return wait();
     }
@@ -235,19 +258,26 @@ public:
     // read-back) with its completion event recorded.
     // max_res_bytes: the largest job posted on the worker (a synchronous run()
     // keeps kResMaxBytes: one workgroup is slower than a launch's many above it).
+    // extra_views: a view per extra descriptor (shorter: the rest unchecked), or
+    // nullptr; a job with a checked frame always launches (the pieces kernel
+    // with the check).
     kmws_status launch(uint8_t* extra_base = nullptr, uint64_t extra_span = 0,
                        const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr,
-                       uint64_t max_res_bytes = kResMaxBytesAsync)
+                       uint64_t max_res_bytes = kResMaxBytesAsync, const std::vector<Utf8View>* extra_views = nullptr)
     {
         const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
         if (n1 + n2 == 0) return KMWS_OK;
         if (launched_) return KMWS_ERR_INVALID_STATE;
+        bool checked = !views_.empty();
+        if (extra_views)
+            for (size_t i = 0; i < extra_views->size() && i < n2; ++i) checked |= ((*extra_views)[i].w & kUtf8Checked) != 0u;
+        if (!checked) extra_views = nullptr;
         for (size_t i = 0; i < n2; ++i)
             if ((*extra)[i].off + (*extra)[i].len > extra_span) return KMWS_ERR_INVALID_PARAM;
         if (n2 && !extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
         if (n2 && !extra_dv) return KMWS_ERR_INVALID_PARAM;  // must be pinned
         if (n1 && !dv_h_) return KMWS_ERR_FAILED;
-        if (n1 + n2 <= (size_t)kResMaxDescs) {
+        if (!checked && n1 + n2 <= (size_t)kResMaxDescs) {
             const kmws_status st = resident_post(device_, descs_.data(), dv_h_, n1, n2 ? extra->data() : nullptr,
                                                  extra_dv, n2, &res_, max_res_bytes);
             if (st == KMWS_OK) {  // kept for a launch if the worker withdraws the job
@@ -261,7 +291,7 @@ public:
             }
             if (st != KMWS_ERR_NOT_SUPPORTED) return st;
         }
-        return launch_kernels(extra_base, extra_span, extra, extra_dv);
+        return launch_kernels(extra_base, extra_span, extra, extra_dv, checked, extra_views);
     }
 
 private:
@@ -282,7 +312,8 @@ private:
     }
 
     kmws_status launch_kernels(uint8_t* extra_base, uint64_t extra_span, const std::vector<kmws_desc>* extra,
-                               uint8_t* extra_dv)
+                               uint8_t* extra_dv, bool checked = false,
+                               const std::vector<Utf8View>* extra_views = nullptr)
     {
         const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
         if (n1 + n2 == 0) return KMWS_OK;
@@ -304,6 +335,7 @@ private:
         if (p1 + p2 > 0x7FFFFFFFull) return KMWS_ERR_INVALID_PARAM;
         kmws_status st = ensure_host(n1 + n2, p1 + p2);
         if (st != KMWS_OK) return st;
+        if (checked) return launch_checked(extra_base, eb, delta, extra, extra_dv, extra_views, p1, p2, bytes);
         std::memcpy(h_desc_, descs_.data(), n1 * sizeof(kmws_desc));
         size_t k = 0;
         for (size_t i = 0; i < n1; ++i)
@@ -341,7 +373,68 @@ private:
         return KMWS_OK;
     }
 
-    // Pinned descriptor and piece arrays (and their device views) for nd / np entries.
+    // The checked form of launch_kernels (after its argument checks and
+    // ensure_host): descriptors, views and zeroed verdict bytes, and a piece list
+    // whose records carry the four still-masked bytes before each piece j >= 1
+    // -- read here, from host memory, before anything is launched.
+    kmws_status launch_checked(uint8_t* extra_base, uint8_t* eb, uint64_t delta, const std::vector<kmws_desc>* extra,
+                               uint8_t* extra_dv, const std::vector<Utf8View>* extra_views, uint64_t p1, uint64_t p2,
+                               uint64_t bytes)
+    {
+        const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
+        if (n_slots_ > n1 + n2) return KMWS_ERR_INVALID_STATE;  // a slot without its descriptor
+        views_.resize(n1, Utf8View{0u, 0u});
+        if (n1) {
+            std::memcpy(h_desc_, descs_.data(), n1 * sizeof(kmws_desc));
+            std::memcpy(h_view_, views_.data(), n1 * sizeof(Utf8View));
+        }
+        std::memset(h_verdict_, 0, n1 + n2);
+        PieceRecEdge* pe = reinterpret_cast<PieceRecEdge*>(h_piece_);
+        auto add_pieces = [&](const uint8_t* host, const kmws_desc& x, uint32_t idx, size_t k) {
+            for (uint64_t j = 0, c = piece_count(x.off, x.len); j < c; ++j) {
+                uint32_t edge = 0;
+                if (j) std::memcpy(&edge, host + 16 * ((x.off >> 4) + j * kPieceWords) - 4, 4);
+                pe[k++] = PieceRecEdge{idx, (uint32_t)j, edge};
+            }
+            return k;
+        };
+        size_t k = 0;
+        for (size_t i = 0; i < n1; ++i) k = add_pieces(h_, descs_[i], (uint32_t)i, k);
+        for (size_t i = 0; i < n2; ++i) {
+            kmws_desc x = (*extra)[i];
+            x.off += delta;
+            h_desc_[n1 + i] = x;
+            Utf8View v = extra_views && i < extra_views->size() ? (*extra_views)[i] : Utf8View{0u, 0u};
+            if (!(v.w & kUtf8Checked) || v.slot >= n_slots_) v = Utf8View{0u, 0u};
+            h_view_[n1 + i] = v;
+            k = add_pieces(eb, x, (uint32_t)i, k);
+        }
+        kmws_status st = KMWS_OK;
+        if (p1) {
+            if (!dv_h_) return KMWS_ERR_FAILED;
+            st = launch_unmask_pieces_utf8(dv_h_, dv_desc_, dv_view_, dv_piece_edge(), (uint32_t)p1, dv_verdict_,
+                                           stream_);
+            if (st != KMWS_OK) return st;
+        }
+        if (p2) {
+            if (!extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
+            if (!extra_dv) return KMWS_ERR_INVALID_PARAM;
+            st = launch_unmask_pieces_utf8(extra_dv - delta, dv_desc_ + n1, dv_view_ + n1, dv_piece_edge() + p1,
+                                           (uint32_t)p2, dv_verdict_, stream_);
+            if (st != KMWS_OK) return st;
+        }
+        if (hipEventRecord(done_, stream_) != hipSuccess) return KMWS_ERR_FAILED;
+        spin_us_ = std::min<uint64_t>(2000, std::max<uint64_t>(1000, 2 * (20 + (bytes >> 13))));  // as launch_kernels
+        launched_ = true;
+        return KMWS_OK;
+    }
+    PieceRecEdge* dv_piece_edge() const { return reinterpret_cast<PieceRecEdge*>(dv_piece_); }
+
+    // Pinned descriptor and piece arrays (and their device views) for nd / np
+    // entries.  Each allocation also holds what the checked launch adds for its
+    // entries, so that the check brings no hipHostMalloc of its own into a loop
+    // iteration: behind the c descriptors their c views and c verdict bytes; a
+    // piece entry has room for the wider PieceRecEdge.
     kmws_status ensure_host(size_t nd, size_t np)
     {
         if (nd > desc_cap_) {
@@ -349,12 +442,18 @@ private:
             if (h_desc_) (void)hipHostFree(h_desc_);
             h_desc_ = nullptr;
             dv_desc_ = nullptr;
+            h_view_ = dv_view_ = nullptr;
+            h_verdict_ = dv_verdict_ = nullptr;
             desc_cap_ = 0;
-            if (hipHostMalloc(reinterpret_cast<void**>(&h_desc_), c * sizeof(kmws_desc), hipHostMallocDefault) !=
-                hipSuccess)
+            if (hipHostMalloc(reinterpret_cast<void**>(&h_desc_),
+                              c * (sizeof(kmws_desc) + sizeof(Utf8View) + 1), hipHostMallocDefault) != hipSuccess)
                 return KMWS_ERR_FAILED;
             dv_desc_ = static_cast<kmws_desc*>(device_view(h_desc_));
             if (!dv_desc_) return KMWS_ERR_FAILED;
+            h_view_ = reinterpret_cast<Utf8View*>(h_desc_ + c);
+            dv_view_ = reinterpret_cast<Utf8View*>(dv_desc_ + c);
+            h_verdict_ = reinterpret_cast<uint8_t*>(h_view_ + c);
+            dv_verdict_ = reinterpret_cast<uint8_t*>(dv_view_ + c);
             desc_cap_ = c;
         }
         if (np > piece_cap_) {
@@ -363,7 +462,8 @@ private:
             h_piece_ = nullptr;
             dv_piece_ = nullptr;
             piece_cap_ = 0;
-            if (hipHostMalloc(reinterpret_cast<void**>(&h_piece_), c * sizeof(PieceRec), hipHostMallocDefault) !=
+            static_assert(sizeof(PieceRecEdge) >= sizeof(PieceRec), "one array serves both launches");
+            if (hipHostMalloc(reinterpret_cast<void**>(&h_piece_), c * sizeof(PieceRecEdge), hipHostMallocDefault) !=
                 hipSuccess)
                 return KMWS_ERR_FAILED;
             dv_piece_ = static_cast<PieceRec*>(device_view(h_piece_));
@@ -400,8 +500,14 @@ private:
     uint8_t* dv_h_ = nullptr;
     size_t cap_ = 0, len_ = 0;
     std::vector<kmws_desc> descs_;
+    std::vector<Utf8View> views_;  // empty: no staged descriptor is checked; else one per descriptor so far
+    uint32_t n_slots_ = 0;         // verdict bytes handed out (utf8_slot)
     kmws_desc* h_desc_ = nullptr;   // pinned, read by the kernel over PCIe
     kmws_desc* dv_desc_ = nullptr;  // its device view
+    Utf8View* h_view_ = nullptr;    // behind the descriptors, in their allocation
+    Utf8View* dv_view_ = nullptr;
+    uint8_t* h_verdict_ = nullptr;  // behind the views: written by the checked launch, read after wait()
+    uint8_t* dv_verdict_ = nullptr;
     size_t desc_cap_ = 0;
     PieceRec* h_piece_ = nullptr;
     PieceRec* dv_piece_ = nullptr;

@@ -820,6 +820,88 @@ __global__ void __launch_bounds__(kBlock) unmask_utf8_tail_kernel(uint8_t* __res
                                    s_key, s_row, nullptr);
 }
 
+// ---- the host path: kmws_decoder_set_utf8_check (kmws_decoder.cpp) ----
+//
+// unmask_pieces_kernel (kmws_unmask.hip) with the validation in its pass: block
+// b handles piece pieces[b] of one frame's 16-byte aligned hull, 256 lanes x 4
+// words, word w0 + tid + 256 i -- so a wave-instruction loads one 1 KiB row, row
+// = wave + 4 i, the layout fused_lookback hands over.  The frame's message
+// state is not scanned for here: the host decoder walks each connection's
+// frames in order and passes the view (kmws_utf8_stream.hpp).  The unmask is the
+// pieces kernel's, byte for byte; a key of 0 stores nothing (an unmasked frame
+// of a CLIENT-mode decoder is only checked).  The look-back of the piece's
+// first word is `edge`, which the HOST read before the launch: the piece before
+// belongs to another block, which may or may not have stored those bytes
+// unmasked already (the race of the fused in-place pass above; here every
+// payload lies in host memory, so the host reads the 4 bytes while it builds the
+// piece list and no pre-pass kernel is needed).  Piece 0 starts at the frame's
+// first byte and takes its look-back from the view.  A rejected byte is
+// reported with a plain byte store of 1 to the frame's verdict byte in pinned
+// host memory, at most one lane per wave; the host zeroes the bytes before the
+// launch and reads them after its wait.
+static_assert(kPieceWords == kUtf8V * kBlock, "a piece is a tile of the validator: fused_lookback's rows");
+__global__ void __launch_bounds__(kBlock) unmask_pieces_utf8_kernel(uint8_t* __restrict__ base,
+                                                                    const kmws_desc* __restrict__ d,
+                                                                    const Utf8View* __restrict__ views,
+                                                                    const PieceRecEdge* __restrict__ pieces,
+                                                                    uint8_t* __restrict__ verdict)
+{
+    constexpr int V = kUtf8V;
+    __shared__ uint32_t s_row[kFusedRows];
+    const PieceRecEdge pr = pieces[blockIdx.x];
+    const kmws_desc x = d[pr.frame];
+    const Utf8View fv = views[pr.frame];
+    const uint64_t end = x.off + x.len;
+    const uint64_t w0 = (x.off >> 4) + (uint64_t)pr.piece * kPieceWords;
+    const uint64_t wh = (end + 15) >> 4;
+    const uint64_t w1 = wh < w0 + kPieceWords ? wh : w0 + kPieceWords;
+    const uint32_t r = rot_key(x.key, x.off);
+    u32x4 v[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
+        v[i] = w < w1 ? *reinterpret_cast<const u32x4*>(base + 16 * w) : u32x4{0, 0, 0, 0};
+    }
+    if (x.key != 0u) {  // block-uniform
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
+            if (w >= w1) continue;
+            const uint64_t a = 16 * w;
+            if (a >= x.off && a + 16 <= end) {
+                *reinterpret_cast<u32x4*>(base + a) = v[i] ^ r;
+            } else {  // the hull's first or last word: own bytes only
+                const uint64_t lo = a > x.off ? a : x.off, hi = a + 16 < end ? a + 16 : end;
+                for (uint64_t q = lo; q < hi; ++q) {
+                    const uint32_t b = (uint32_t)(q - a);
+                    const uint32_t dw = (b & 8u) ? ((b & 4u) ? v[i].w : v[i].z) : ((b & 4u) ? v[i].y : v[i].x);
+                    base[q] = (uint8_t)((dw ^ r) >> (8 * (b & 3u)));
+                }
+            }
+        }
+    }
+    if (!(fv.w & kUtf8Checked)) return;  // block-uniform: binary, RSV1 and control frames end here
+    uint32_t prev[V];
+    fused_lookback(v, pr.piece ? pr.edge : 0u, s_row, prev);
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
+        if (w < w1) bad |= fused_word_frame_bad(v[i], prev[i], 16 * w, x.off, end, r, fv.w);  // past the hull: nothing
+    }
+    const unsigned long long m = __ballot(bad);  // one report per wave
+    if (m != 0ull && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) verdict[fv.slot] = (uint8_t)1;
+}
+
+kmws_status launch_unmask_pieces_utf8(uint8_t* base, const kmws_desc* descs, const Utf8View* views,
+                                      const PieceRecEdge* pieces, uint32_t np, uint8_t* verdict, hipStream_t s)
+{
+    if (np == 0) return KMWS_OK;
+    if (!base || !descs || !views || !pieces || !verdict) return KMWS_ERR_INVALID_PARAM;
+    hipLaunchKernelGGL(unmask_pieces_utf8_kernel, dim3(np), dim3(kBlock), 0, s, base, descs, views, pieces, verdict);
+    return hip_status(hipGetLastError());
+}
+
 static bool have_device()
 {
     static const bool have = kmws_device_count() > 0;

@@ -32,7 +32,7 @@ DEVICE_POLICY_NUMA, DEVICE_POLICY_ROUND_ROBIN, DEVICE_POLICY_FIRST = 0, 1, 2
 EXPORTS = [
     "kmws_encode_header", "kmws_header_size", "kmws_decoder_create", "kmws_decoder_destroy",
     "kmws_decoder_set_mode", "kmws_decoder_reset", "kmws_decoder_feed", "kmws_device_count",
-    "kmws_decoder_set_in_place",
+    "kmws_decoder_set_in_place", "kmws_decoder_set_utf8_check", "kmws_frame_utf8",
     "kmws_unmask_workspace_size", "kmws_unmask_batch", "kmws_unmask_plan", "kmws_unmask_apply",
     "kmws_unmask_autotune", "kmws_unmask_apply_sched", "kmws_unmask_default_schedule", "kmws_read_status",
     "kmws_copy_workspace_size", "kmws_encode_batch",
@@ -125,6 +125,8 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_decoder_set_mode": (None, [vp, i32]),
         "kmws_decoder_reset": (None, [vp]),
         "kmws_decoder_set_in_place": (None, [vp, i32]),
+        "kmws_decoder_set_utf8_check": (None, [vp, i32]),
+        "kmws_frame_utf8": (C.c_uint8, [C.POINTER(FrameHdr)]),
         "kmws_decoder_feed": (i32, [vp, u8p, sz, FRAME_CB, vp]),
         "kmws_device_count": (i32, []),
         "kmws_unmask_workspace_size": (sz, [u64]),
@@ -255,6 +257,7 @@ class Header:
     length: int = 0
     plen: int = 0
     xpl64: int = 0
+    utf8: int = 0  # UTF8_* during the frame callback of a handler with setUtf8Check(True); else 0
 
     def to_c(self) -> FrameHdr:
         h = FrameHdr()
@@ -268,7 +271,7 @@ class Header:
     @staticmethod
     def from_c(h: FrameHdr) -> "Header":
         return Header(h.fin, h.rsv1, h.rsv2, h.rsv3, h.opcode, h.mask, bytes(h.maskey), h.length,
-                      h.plen, h.xpl64)
+                      h.plen, h.xpl64, h.reserved)
 
 
 def encode_frame_header(hdr: Header) -> bytes:
@@ -330,6 +333,11 @@ class WSHandler:
     def setInPlace(self, on: bool) -> None:
         """kmws_decoder_set_in_place (default True)."""
         lib().kmws_decoder_set_in_place(self._d, int(bool(on)))
+
+    def setUtf8Check(self, on: bool) -> None:
+        """kmws_decoder_set_utf8_check (default off): the callback's Header.utf8
+        holds UTF8_NOT_TEXT / OK / BAD / AFTER_BAD.  Switch between messages only."""
+        lib().kmws_decoder_set_utf8_check(self._d, int(bool(on)))
 
     def handleData(self, data) -> int:
         n = len(data)
