@@ -571,9 +571,8 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  * checks it); the byte offset of the error; the resident grid does not know the
  * rule (the host path has the check through kmws_decoder_set_utf8_check, and
  * launches the generations that hold a checked frame instead of posting them
- * to the grid); the gather form
- * (kmws_unpack_gather) has no fused validation (the in-place unmask has:
- * kmws_unmask_utf8_batch below). */
+ * to the grid).  The in-place unmask and the gather have the check fused into
+ * their payload pass: kmws_unmask_utf8_batch and kmws_gather_unmask_utf8 below. */
 kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
                                const uint16_t* flags, uint32_t n, int payload_masked,
                                const uint32_t* stream_first, uint32_t n_streams,
@@ -626,6 +625,56 @@ kmws_status kmws_unpack_unmask_utf8(uint8_t* wire, uint64_t wire_len, const uint
                                     const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes,
                                     int schedule, void* stream);
+
+/* ---- gather, unmask and UTF-8 validation in one pass over the payload ----
+ * kmws_gather_unmask followed by kmws_utf8_validate on its dense output reads
+ * that output back right after writing it; these entries validate the words the
+ * gather stores from the registers that hold them.
+ *
+ * Workspace bytes: kmws_copy_workspace_size(n, dst_cap) (rounded up to 256) plus
+ * the validator's per-frame and per-stream arrays (about 12 B per frame, 8 B
+ * per stream) -- not its tile plan. */
+size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams);
+
+/* The two contracts composed.  dst, dst_off and the status word are exactly
+ * what kmws_gather_unmask leaves for the same src / descs / n / dst / dst_cap
+ * (the cap rule: total > dst_cap sets status bit 1 and stores nothing; bit 4 on
+ * a look-back timeout); src is never written, src and dst do not overlap, the
+ * descriptors need no order in src.  out_utf8 and carry_out are exactly what
+ * kmws_utf8_validate(dst, dst_off[n], D, flags, n, 0, stream_first, n_streams,
+ * carry_in, carry_out, ..) writes after the plain gather, with D[i] =
+ * {dst_off[i], descs[i].len, 0}.  The verdict is advisory: a BAD message is
+ * gathered like any other.  flags / stream_first / carry_in / carry_out:
+ * kmws_utf8_validate's; a malformed stream_first sets status bit 1 (nothing is
+ * stored then).  With status bit 1 or 4 set out_utf8 / carry_out are not valid.
+ * Stream-ordered, no host sync, no allocation, kernel nodes only (capturable);
+ * the status word is cleared by a kernel.  KMWS_ERR_INVALID_PARAM for a NULL
+ * required pointer (dst_off and workspace always; src, descs, flags, dst,
+ * out_utf8 with frames), a misaligned src / dst, n or n_streams >= 2^31, NULL
+ * stream_first with n_streams != 1, n_streams == 0 with frames; then
+ * KMWS_ERR_BUFFER_TOO_SMALL; then KMWS_ERR_NOT_SUPPORTED without a gfx950
+ * device (no CPU fallback).  n == 0: KMWS_OK, dst_off[0] = 0, carry_out =
+ * carry_in. */
+kmws_status kmws_gather_unmask_utf8(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,
+                                    uint8_t* dst, uint64_t dst_cap, uint64_t* dst_off,
+                                    const uint32_t* stream_first, uint32_t n_streams,
+                                    const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream);
+
+/* kmws_unpack_gather with the validation in its payload pass.  out_desc,
+ * out_flags (required here), out_err, dst, dst_off and status bits 1, 2 and 4
+ * are exactly as after kmws_unpack_gather; out_utf8 and carry_out are exactly
+ * kmws_utf8_validate applied to the dense output and the out_flags this call
+ * writes.  A frame with a header error is what kmws_unpack_gather makes of it
+ * -- len 0, flags as parsed -- and is judged as such an empty frame: look at
+ * out_err (or status bit 2, with which out_utf8 / carry_out stay valid) before
+ * out_utf8.  Also KMWS_ERR_INVALID_PARAM for a bad mode. */
+kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                    int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                    uint8_t* dst, uint64_t dst_cap, uint64_t* dst_off,
+                                    const uint32_t* stream_first, uint32_t n_streams,
+                                    const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- host-resident batches: pinned H2D -> kernel -> D2H pipeline ---- */
 typedef struct kmws_pipeline kmws_pipeline;

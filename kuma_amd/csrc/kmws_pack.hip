@@ -20,13 +20,18 @@
 // validates one header per frame with the reference's rules
 // (WSHandler.cpp:118-234, including the 127-length quirk); the payload is then
 // unmasked in place (kmws_unmask_batch) or gathered + unmasked into a dense
-// arena by the same copy kernels (kmws_gather_unmask).
+// arena by the same copy kernels (kmws_gather_unmask).  The gather's validating
+// form (kmws_gather_unmask_utf8, kmws_unpack_gather_utf8): the same copy
+// kernels check the words of text messages, from the registers that hold them
+// after their stores, against the UTF-8 rule (kmws_utf8_dev.hpp) -- the
+// verdicts kmws_utf8_validate gives on the dense output, without reading it back.
 // Header-only pack (kmws_pack_headers, kuma's iovec form): each header into a
 // 16-byte slot, with the wire offsets after reduce_kernel.  Boundary discovery on the
 // device (kmws_find_headers_streams): the serial header-chain walk, one lane
 // per stream.
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
+#include "kmws_utf8_dev.hpp"
 
 namespace kmws {
 
@@ -475,6 +480,45 @@ __device__ __forceinline__ void put_frame(u32x4& out, uint64_t a, const FrameGeo
     }
 }
 
+// ---- the validating gather (kmws_gather_unmask_utf8) ----
+// What the validating forms of the copy kernels read besides the copy's own
+// arguments: each frame's view and the verdict words (kmws_utf8_dev.hpp), and
+// the frames in output space -- frame g is [start[g], start[g] + d[g].len).
+struct Utf8Gather {
+    const Utf8View* views;
+    uint32_t* first_bad;
+    const kmws_desc* d;
+    const uint64_t* start;
+    uint32_t n;
+};
+struct NoUtf8 {};
+
+// The output word v at output byte a against every checked frame from `g0` on
+// that has bytes in it -- the words that hold a frame edge (the unit form's
+// edge words, every word of chunk_dense_kernel).  The dword before the word is
+// rebuilt per frame from that frame's own SOURCE bytes, still masked: never
+// from dst, which another wave may or may not have stored yet, and only where
+// the frame reaches back (word_bad uses no other byte of it).
+__device__ __forceinline__ void check_word_frames(const u32x4& v, uint64_t a, uint32_t g0,
+                                                  const uint8_t* __restrict__ src, const Utf8Gather& u)
+{
+    for (uint32_t g = g0; g < u.n; ++g) {
+        const uint64_t s = u.start[g];
+        if (s >= a + 16u) break;
+        const kmws_desc dg = u.d[g];
+        if (dg.len == 0u || s + dg.len <= a) continue;
+        const Utf8View gv = u.views[g];
+        if (!(gv.w & kUtf8Checked)) continue;
+        uint32_t prev = 0;
+        for (uint32_t k = 1; k <= 3u && a >= s + k; ++k) {
+            const uint64_t j = a - k - s;  // payload byte j of frame g = output byte a - k
+            const uint32_t b = src[dg.off + j] ^ ((dg.key >> (8u * (uint32_t)(j & 3u))) & 0xFFu);
+            prev |= b << (8u * (4u - k));
+        }
+        if (plain_word_frame_bad(v, prev, a, s, s + dg.len, gv.w)) report_bad(u.first_bad, gv.slot, g);
+    }
+}
+
 // A frame's unit geometry for the slot-parallel record pass (LDS), word
 // indices relative to its first unit base b0.
 struct FrameUnits {
@@ -775,6 +819,7 @@ __device__ __forceinline__ UnitInfo decode_unit(const UnitRec& r, bool live, con
 // shifted source run of 1 KiB per wave instruction starts mid-line, so two
 // instructions (or two waves) share its edge lines.
 constexpr int kUnitW = kUnitWords / 64;  // words per lane
+static_assert(kUnitW == 4, "copy_body selects an edge word among four");
 struct UnitRegs {
     u32x4 lo[kUnitW];  // aligned source word of each of the lane's output words
     u32x4 ex;          // the source word after the last interior word (every lane: one address)
@@ -821,8 +866,11 @@ __device__ __forceinline__ u32x4 readlane0(const u32x4& v)
 
 // Composes and stores a unit whose loads unit_issue issued: every owned word of
 // the unit, each 64-byte granule by one store instruction.
+// keep (the validating form): receives the lane's output words 64 i + lane as
+// composed (every owned word, stored or not).
+template <bool KEEP = false>
 __device__ __forceinline__ void unit_finish(const UnitInfo& x, int lane, uint8_t* __restrict__ dst, uint64_t total,
-                                            const UnitRegs& R)
+                                            const UnitRegs& R, u32x4* keep = nullptr)
 {
     // Every register the unit loaded is consumed here on every path, so the wait
     // for them is a counted one and no load into these registers stays pending
@@ -878,16 +926,60 @@ __device__ __forceinline__ void unit_finish(const UnitInfo& x, int lane, uint8_t
         if (k >= x.klo && k < x.khi && a + 16 <= total)
             __builtin_nontemporal_store(out[i], reinterpret_cast<u32x4*>(dst + a));
     }
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int i = 0; i < kUnitW; ++i) keep[i] = out[i];
+    }
+}
+
+// The dword before a wave's first output word at output byte a0, for the
+// validating forms: lanes 0-3 each load one byte of it, still masked, from
+// source byte p[lane - 4] (p: the source byte of output byte a0; `have`, per
+// lane: that byte exists -- it need not belong to the frame holding a0: the
+// rule uses the bytes of the dword that do).  Issued with the wave's other
+// loads, ahead of its stores.
+__device__ __forceinline__ uint32_t lookback_issue(const uint8_t* p, bool have, int lane)
+{
+    uint32_t b = 0;
+    if (lane < 4 && have) b = p[lane - 4];
+    return b;
+}
+// The four bytes as a dword, unmasked with the rotated key of aligned output words.
+__device__ __forceinline__ uint32_t lookback_dword(uint32_t b, uint32_t rk)
+{
+    return ((uint32_t)__shfl((int)b, 0, 64) | (uint32_t)__shfl((int)b, 1, 64) << 8 |
+            (uint32_t)__shfl((int)b, 2, 64) << 16 | (uint32_t)__shfl((int)b, 3, 64) << 24) ^ rk;
+}
+// The dword before each of the lane's words 64 i + lane: the neighbour lane's
+// word, lane 0 from lane 63 of the instruction before; `edge` for word `first`.
+template <int W>
+__device__ __forceinline__ void prev_dwords(const u32x4 (&out)[W], int lane, uint32_t first, uint32_t edge,
+                                            uint32_t (&prev)[W])
+{
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        uint32_t up = (uint32_t)__shfl_up((int)out[i].w, 1, 64);
+        if (i > 0) {
+            const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)out[i > 0 ? i - 1 : 0].w, 63);
+            if (lane == 0) up = last;
+        }
+        prev[i] = (uint32_t)(64 * i + lane) == first ? edge : up;
+    }
 }
 
 // One wave per unit: kUnitW words per lane, 1 KiB per wave-instruction.
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                      const V2* __restrict__ tot,
-                                                      const UnitRec* __restrict__ rec,
-                                                      const u32x4* __restrict__ edge,
-                                                      const WsHead* __restrict__ head, uint64_t unit_base,
-                                                      uint32_t split)
+// UTF8 (the validating gather): the unit's words are stored exactly as without
+// it; then the words of checked frames are validated from the registers that
+// hold them, in output space.  Interior words belong to the unit's frame
+// (wave-uniform: its start, length and view are scalar loads issued ahead of
+// the payload); edge words walk their frames (check_word_frames).  The dword
+// before the unit's first owned word comes from the source (lookback_issue).
+// A unit of an unchecked frame without edge words ends after its stores.
+template <bool HEADERS, bool UTF8, class U>
+__device__ __forceinline__ void copy_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                          const V2* __restrict__ tot, const UnitRec* __restrict__ rec,
+                                          const u32x4* __restrict__ edge, const WsHead* __restrict__ head,
+                                          uint64_t unit_base, uint32_t split, const U& ug)
 {
     const int lane = threadIdx.x & 63;
     // wave id through readfirstlane: provably uniform, so the record is one scalar load
@@ -921,8 +1013,74 @@ __global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict_
     // Every load is issued before the first store (vmcnt also counts stores, so
     // a load issued after a store would make its wait cover that store too).
     UnitRegs R;
-    unit_issue(x, lane, src, edge + (uint64_t)x.f * kEdgeWords, R);
-    unit_finish(x, lane, dst, total, R);
+    if constexpr (!UTF8) {
+        unit_issue(x, lane, src, edge + (uint64_t)x.f * kEdgeWords, R);
+        unit_finish(x, lane, dst, total, R);
+    } else {
+        static_assert(!HEADERS, "the validating form is the gather's");
+        // the frame in output space and its view: scalar loads, in flight under the payload's
+        const uint64_t fs = ug.start[x.f];
+        const uint32_t flen = ug.d[x.f].len;
+        const Utf8View fv = ug.views[x.f];
+        unit_issue(x, lane, src, edge + (uint64_t)x.f * kEdgeWords, R);
+        // the first owned word's first byte lies in the frame (its granule's first
+        // byte does): the source holds the bytes before it wherever the frame does
+        const uint64_t so = r.src + 16ull * x.klo;
+        const uint32_t lb = lookback_issue(src + so, so + (uint32_t)lane >= 4u, lane);
+        // taken before the first store: a wait for its load behind them would wait for the stores too
+        const uint32_t edge_dw = lookback_dword(lb, x.rk);
+        u32x4 out[kUnitW];
+        unit_finish<true>(x, lane, dst, total, R, out);
+        const uint32_t nslow = (x.ilo - x.klo) + (x.khi - x.ihi);
+        const bool chk = (fv.w & kUtf8Checked) != 0u && flen != 0u;
+        if (!chk && nslow == 0u) return;  // wave-uniform: binary, RSV1 and control frames end here
+        uint32_t prev[kUnitW];
+        prev_dwords<kUnitW>(out, lane, x.klo, edge_dw, prev);
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < kUnitW; ++i) {
+            const uint32_t k = lane + 64 * i;
+            const uint64_t a = x.dst + 16u * k;
+            if (chk && k >= x.ilo && k < x.ihi && a < total)
+                bad |= plain_word_frame_bad(out[i], prev[i], a, fs, fs + flen, fv.w);
+        }
+        const unsigned long long m = __ballot(bad);  // one report per wave
+        if (m != 0ull && lane == __ffsll((long long)m) - 1) report_bad(ug.first_bad, fv.slot, x.f);
+        if (nslow == 0u) return;  // wave-uniform
+        // the edge words (a frame's last unit): one rolled loop, compact code
+#pragma unroll 1
+        for (int i = 0; i < kUnitW; ++i) {
+            const uint32_t k = lane + 64 * i;
+            const uint64_t a = x.dst + 16u * k;
+            const u32x4 w = i == 0 ? out[0] : (i == 1 ? out[1] : (i == 2 ? out[2] : out[3]));
+            const bool edge_word = (k >= x.klo && k < x.ilo) || (k >= x.ihi && k < x.khi);
+            if (edge_word && a < total) check_word_frames(w, a, x.f, src, ug);
+        }
+    }
+}
+
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                      const V2* __restrict__ tot,
+                                                      const UnitRec* __restrict__ rec,
+                                                      const u32x4* __restrict__ edge,
+                                                      const WsHead* __restrict__ head, uint64_t unit_base,
+                                                      uint32_t split)
+{
+    copy_body<HEADERS, false>(src, dst, tot, rec, edge, head, unit_base, split, NoUtf8{});
+}
+
+// Registers ("the validating gather"): 98 VGPRs, 4 waves per SIMD, no
+// scratch.  Asking the allocator for the 5 waves per SIMD that the large-frame
+// launches' dynamic LDS allows costs 12 B of scratch per lane.
+__global__ void __launch_bounds__(kBlock) copy_utf8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                           const V2* __restrict__ tot,
+                                                           const UnitRec* __restrict__ rec,
+                                                           const u32x4* __restrict__ edge,
+                                                           const WsHead* __restrict__ head, uint64_t unit_base,
+                                                           uint32_t split, Utf8Gather u)
+{
+    copy_body<false, true>(src, dst, tot, rec, edge, head, unit_base, split, u);
 }
 
 __device__ __forceinline__ u32x4 shfl16_down1(const u32x4& v)
@@ -954,6 +1112,7 @@ constexpr uint64_t kChunkBytes = 16ull * kChunkWords;
 constexpr uint32_t kSlowShift = 9;  // boundary-list entry: word | table frame << kSlowShift
 constexpr uint32_t kSlowWord = (1u << kSlowShift) - 1;
 static_assert(kChunkW == 4 || kChunkW == 8, "chunk: 4 or 8 words per lane");
+static_assert(kChunkW == 4, "chunk_body (the validating form) selects a word among four");
 constexpr uint32_t kChunkFrames = 64;           // a chunk's frame table, one lane per frame
 
 __host__ __device__ __forceinline__ uint64_t chunk_count(uint64_t bytes) { return (bytes + kChunkBytes - 1) / kChunkBytes; }
@@ -1015,7 +1174,7 @@ struct ChunkFrame {
     uint32_t rk;         // rot_key(key, p0) (0: no mask)
     uint64_t sbase;      // source byte of output offset o = sbase + o
     uint8_t h[16];       // the header's bytes (encode)
-    uint64_t pad;
+    uint64_t pad;        // the validating gather: the frame's Utf8View (slot, then w)
 };
 static_assert(sizeof(ChunkFrame) == 48, "ChunkFrame is three 16-byte LDS loads");
 
@@ -1058,15 +1217,21 @@ __device__ __forceinline__ u32x4 copy_src_load(const uint8_t* p)
 
 // One wave per 4 KiB output chunk (4 words per lane, 1 KiB per instruction).
 // A chunk meeting more than kChunkFrames frames is listed for chunk_dense_kernel.
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                            const kmws_desc* __restrict__ d,
-                                                            const uint16_t* __restrict__ flags, uint32_t n,
-                                                            const uint64_t* __restrict__ start,
-                                                            const uint32_t* __restrict__ cmap,
-                                                            const V2* __restrict__ tot, WsHead* __restrict__ head,
-                                                            uint32_t* __restrict__ dense, uint64_t chunk_base,
-                                                            uint32_t split)
+// UTF8 (the validating gather): each frame's view rides in its table entry
+// (loaded with its descriptor), so after the four stores the rule reads
+// registers and LDS only; a chunk whose frames are all unchecked ends after the
+// stores.  Interior words run the word test against their one frame, boundary
+// words walk the table's frames that reach into them.  The dword before the
+// chunk's first word comes from the source (lookback_issue).  A chunk with more
+// than 64 boundary words (whose surplus is stored from LDS, not from the
+// registers validated here) goes to chunk_dense_kernel as well.
+template <bool HEADERS, bool UTF8, class U>
+__device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                           const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
+                                           uint32_t n, const uint64_t* __restrict__ start,
+                                           const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
+                                           WsHead* __restrict__ head, uint32_t* __restrict__ dense,
+                                           uint64_t chunk_base, uint32_t split, const U& u)
 {
     __shared__ ChunkFrame s_tab[kBlock / 64][kChunkFrames];
     __shared__ uint16_t s_slow[kBlock / 64][kChunkWords];  // boundary words: word | frame << kSlowShift
@@ -1093,6 +1258,7 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         return;
     }
     ChunkFrame* tab = s_tab[wave];
+    bool chk_lane = false;
     if ((uint32_t)lane < nfr) {
         const uint32_t j = f0 + lane;
         const kmws_desc x = d[j];
@@ -1110,6 +1276,11 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         if (HEADERS) build_header(x.len, fl, key, h0, h1);
         __builtin_memcpy(e.h, &h0, 8);
         __builtin_memcpy(e.h + 8, &h1, 8);
+        if constexpr (UTF8) {
+            const Utf8View gv = u.views[j];
+            e.pad = (uint64_t)gv.slot | (uint64_t)gv.w << 32;
+            chk_lane = (gv.w & kUtf8Checked) != 0u && x.len != 0u;
+        }
         tab[lane] = e;
     }
     wave_lds_sync();
@@ -1149,6 +1320,12 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         nslow += (uint32_t)__builtin_popcountll(bal);
     }
     wave_lds_sync();
+    if constexpr (UTF8) {
+        if (nslow > 64u) {  // wave-uniform
+            if (lane == 0) dense[atomicAdd(&head->pad[0], 1u)] = (uint32_t)c;
+            return;
+        }
+    }
     // Boundary words are composed byte-parallel: one lane per byte, 16 words
     // per batch (four per instruction).  Each byte's frame is found from its
     // word's first frame on; the byte is a header byte (from the table) or a
@@ -1212,6 +1389,11 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         rk[i] = e.rk;
     }
     X = copy_src_load(reinterpret_cast<const uint8_t*>(xa));
+    uint32_t lb = 0;
+    if constexpr (UTF8) {  // output bytes -4 .. -1 where the chunk's first frame holds them
+        const ChunkFrame& e0 = tab[0];
+        lb = lookback_issue(reinterpret_cast<const uint8_t*>(e0.sbase), lane - 4 >= e0.p0 && e0.r1 > 0, lane);
+    }
     // Pass 3: the boundary words
     if (nslow) batch_put(0);
     for (uint32_t g0 = 16; g0 < nslow; g0 += 16) {  // wave-uniform
@@ -1219,8 +1401,13 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         batch_put(g0);
     }
     wave_lds_sync();
+    // the look-back dword is taken before the first store: a wait for its load
+    // behind them would wait for the stores as well
+    uint32_t edge_dw = 0;
+    if constexpr (UTF8) edge_dw = lookback_dword(lb, tab[0].rk);
     // Pass 4: the four full-width stores, boundary words merged in.
     uint32_t seen = 0;
+    u32x4 outv[kChunkW];
 #pragma unroll
     for (int i = 0; i < (int)kChunkW; ++i) {
         const uint32_t k = 64u * i + lane;
@@ -1245,22 +1432,95 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
         }
         if (mine && a + 16 <= total) __builtin_nontemporal_store(out, reinterpret_cast<u32x4*>(dst + a));
         else if (mine && a < total) store_word_bytes(dst, a, total, out);
+        outv[i] = out;
     }
+    if constexpr (UTF8) {
+        if (__ballot(chk_lane) == 0ull) return;  // wave-uniform: binary, RSV1 and control frames end here
+        uint32_t prev[kChunkW];
+        prev_dwords<(int)kChunkW>(outv, lane, 0u, edge_dw, prev);
+        // Which words need the rule (wave-uniform skip of everything else): a
+        // boundary word does; an interior word of a checked frame does unless it is
+        // all ASCII after an ASCII byte -- the byte before it, or the look-back's
+        // last byte at the frame's first byte -- which leaves nothing pending.
+        uint32_t need = 0;
+#pragma unroll
+        for (int i = 0; i < (int)kChunkW; ++i) {
+            const int32_t a = 16 * (int32_t)(64u * i + lane);
+            if (a >= trel) continue;
+            bool nd = (slowbits >> i) & 1u;
+            if (!nd) {
+                const ChunkFrame& e = tab[(uint32_t)(jbits >> (6 * i)) & 63u];
+                const uint32_t vw = (uint32_t)(e.pad >> 32);
+                const uint32_t before = a > e.p0 ? prev[i] >> 24 : vw & 0xFFu;
+                const uint32_t hb = (outv[i].x | outv[i].y | outv[i].z | outv[i].w) & 0x80808080u;
+                nd = (vw & kUtf8Checked) != 0u && (hb != 0u || before >= 0x80u);
+            }
+            need |= nd ? 1u << i : 0u;
+        }
+        if (__ballot(need != 0u) == 0ull) return;
+        // offsets relative to A0, moved up by kBias: word_bad takes unsigned positions
+        constexpr int64_t kBias = 1ll << 31;
+#pragma unroll 1
+        for (int i = 0; i < (int)kChunkW; ++i) {
+            const bool nd = (need >> i) & 1u;
+            if (__ballot(nd) == 0ull) continue;  // wave-uniform
+            const int32_t a = 16 * (int32_t)(64u * i + lane);
+            const u32x4 w = i == 0 ? outv[0] : (i == 1 ? outv[1] : (i == 2 ? outv[2] : outv[3]));
+            const uint32_t pv = i == 0 ? prev[0] : (i == 1 ? prev[1] : (i == 2 ? prev[2] : prev[3]));
+            if (!nd) continue;
+            // the word's first frame, then every frame that starts inside the word
+            for (uint32_t m = (uint32_t)(jbits >> (6 * i)) & 63u; m < nfr; ++m) {
+                const ChunkFrame& e = tab[m];
+                if (e.r0 >= a + 16) break;
+                const uint32_t vw = (uint32_t)(e.pad >> 32);
+                if (e.r1 <= e.p0 || e.r1 <= a || !(vw & kUtf8Checked)) continue;
+                if (plain_word_frame_bad(w, pv, (uint64_t)(a + kBias), (uint64_t)(e.p0 + kBias),
+                                         (uint64_t)(e.r1 + kBias), vw))
+                    report_bad(u.first_bad, (uint32_t)e.pad, f0 + m);
+            }
+        }
+    }
+}
+
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                            const kmws_desc* __restrict__ d,
+                                                            const uint16_t* __restrict__ flags, uint32_t n,
+                                                            const uint64_t* __restrict__ start,
+                                                            const uint32_t* __restrict__ cmap,
+                                                            const V2* __restrict__ tot, WsHead* __restrict__ head,
+                                                            uint32_t* __restrict__ dense, uint64_t chunk_base,
+                                                            uint32_t split)
+{
+    chunk_body<HEADERS, false>(src, dst, d, flags, n, start, cmap, tot, head, dense, chunk_base, split, NoUtf8{});
+}
+
+// Registers: see DESIGN 4 ("the validating gather").
+__global__ void __launch_bounds__(kBlock) chunk_copy_utf8_kernel(const uint8_t* __restrict__ src,
+                                                                 uint8_t* __restrict__ dst,
+                                                                 const kmws_desc* __restrict__ d, uint32_t n,
+                                                                 const uint64_t* __restrict__ start,
+                                                                 const uint32_t* __restrict__ cmap,
+                                                                 const V2* __restrict__ tot, WsHead* __restrict__ head,
+                                                                 uint32_t* __restrict__ dense, uint64_t chunk_base,
+                                                                 uint32_t split, Utf8Gather u)
+{
+    chunk_body<false, true>(src, dst, d, nullptr, n, start, cmap, tot, head, dense, chunk_base, split, u);
 }
 
 // The chunks chunk_copy_kernel listed (more than kChunkFrames frames: regions
 // averaging under 64 bytes): every word byte by byte, its first frame by a
 // binary search over start[].  Correct for any batch, fast only where it does
 // not matter; a batch of small frames takes the unit form instead (below).
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                             const kmws_desc* __restrict__ d,
-                                                             const uint16_t* __restrict__ flags, uint32_t n,
-                                                             const uint64_t* __restrict__ start,
-                                                             const uint32_t* __restrict__ cmap,
-                                                             const V2* __restrict__ tot,
-                                                             const WsHead* __restrict__ head,
-                                                             const uint32_t* __restrict__ dense)
+// UTF8 (the validating gather): every word is also checked against the frames
+// in it (check_word_frames).
+template <bool HEADERS, bool UTF8, class U>
+__device__ __forceinline__ void dense_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                           const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
+                                           uint32_t n, const uint64_t* __restrict__ start,
+                                           const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
+                                           const WsHead* __restrict__ head, const uint32_t* __restrict__ dense,
+                                           const U& u)
 {
     if (head->status & (kStatusBadDesc | kStatusLookbackTimeout)) return;
     const uint32_t cnt = head->pad[0];
@@ -1283,8 +1543,34 @@ __global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __re
             const u32x4 v = compose_word_bytes<HEADERS>(a, lo, n, src, g, fl, d, flags);
             if (a + 16 <= total) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst + a));
             else store_word_bytes(dst, a, total, v);
+            if constexpr (UTF8) check_word_frames(v, a, lo, src, u);
         }
     }
+}
+
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                             const kmws_desc* __restrict__ d,
+                                                             const uint16_t* __restrict__ flags, uint32_t n,
+                                                             const uint64_t* __restrict__ start,
+                                                             const uint32_t* __restrict__ cmap,
+                                                             const V2* __restrict__ tot,
+                                                             const WsHead* __restrict__ head,
+                                                             const uint32_t* __restrict__ dense)
+{
+    dense_body<HEADERS, false>(src, dst, d, flags, n, start, cmap, tot, head, dense, NoUtf8{});
+}
+
+__global__ void __launch_bounds__(kBlock) chunk_dense_utf8_kernel(const uint8_t* __restrict__ src,
+                                                                  uint8_t* __restrict__ dst,
+                                                                  const kmws_desc* __restrict__ d, uint32_t n,
+                                                                  const uint64_t* __restrict__ start,
+                                                                  const uint32_t* __restrict__ cmap,
+                                                                  const V2* __restrict__ tot,
+                                                                  const WsHead* __restrict__ head,
+                                                                  const uint32_t* __restrict__ dense, Utf8Gather u)
+{
+    dense_body<false, true>(src, dst, d, nullptr, n, start, cmap, tot, head, dense, u);
 }
 
 // ------------------------------ header unpack / validate ------------------------------
@@ -1748,6 +2034,31 @@ struct CopyWs {
     uint32_t* dense;  // chunks chunk_copy_kernel left to chunk_dense_kernel
 };
 
+// The validating gather's per-frame kernels (kmws_utf8.hip) run on the source
+// right before the copy grid -- after whatever cleared the status word and, in
+// the unpack form, wrote the descriptors and flags -- and its finish after it.
+struct Utf8Launch {
+    void* arrays;  // utf8_frame_arrays_size(n, n_streams) bytes
+    const uint16_t* flags;
+    uint64_t span;  // of the source: descriptors past it set status bit 1
+    const uint32_t* stream_first;
+    uint32_t n_streams;
+    const kmws_utf8_carry* carry_in;
+    kmws_utf8_carry* carry_out;
+    uint8_t* out;
+};
+static Utf8Gather launch_utf8_before_copy(const Utf8Launch& ul, WsHead* head, const uint8_t* src, const kmws_desc* d,
+                                          const uint64_t* start, uint32_t n, hipStream_t s)
+{
+    const Utf8FrameArrays fa = launch_utf8_frame_state(ul.arrays, head, src, ul.span, d, ul.flags, n, 1,
+                                                       ul.stream_first, ul.n_streams, ul.carry_in, s);
+    return Utf8Gather{fa.views, fa.first_bad, d, start, n};
+}
+static void launch_utf8_after_copy(const Utf8Launch& ul, uint32_t n, hipStream_t s)
+{
+    launch_utf8_frame_finish(ul.arrays, n, ul.stream_first, ul.n_streams, ul.carry_in, ul.carry_out, ul.out, s);
+}
+
 static uint64_t n_tiles(uint32_t n) { return ((uint64_t)n + kScanTile - 1) / kScanTile; }
 static uint64_t n_rows(uint32_t n) { return ((uint64_t)n + kBlock - 1) / kBlock; }
 // sum of unit_bound(R_f) <= total / (16 U) + n (1 + 63 / U) (and total <= cap)
@@ -1810,7 +2121,8 @@ static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, CopyWs& c
 // stream-ordered, nothing on the host in between.
 template <bool HEADERS>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s);
+                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
+                                    const Utf8Launch* ul = nullptr);
 
 // The chunk form's front: one look-back pass (chunk_scan_kernel) in place of
 // reduce + scan + chunk_map (which the fused unpack-gather keeps: its scan
@@ -1820,20 +2132,21 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
 template <bool HEADERS>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                           const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
-                                          hipStream_t s);
+                                          hipStream_t s, const Utf8Launch* ul = nullptr);
 template <bool HEADERS>
 static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                               const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s)
+                               const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
+                               const Utf8Launch* ul = nullptr)
 {
     if (n == 0) {
         if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
         return launch_zero(start, sizeof(uint64_t), s);
     }
-    if (use_chunks(n, cap)) return launch_chunks_one_pass<HEADERS>(src, dst, cap, start, d, flags, n, c, s);
+    if (use_chunks(n, cap)) return launch_chunks_one_pass<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
     const kmws_status st = HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
                                    : launch_reduce(PayloadSize{d}, n, start, c, s);
     if (st != KMWS_OK) return st;
-    return launch_copy_tail<HEADERS>(src, dst, cap, start, d, flags, n, c, s);
+    return launch_copy_tail<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
 }
 
 // The chunk form after the scan: chunk_map, the chunk copy grid, the dense
@@ -1841,14 +2154,15 @@ static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, u
 template <bool HEADERS>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                      const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s);
+                                     hipStream_t s, const Utf8Launch* ul = nullptr);
 template <bool HEADERS>
 static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                                 const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s)
+                                 const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
+                                 const Utf8Launch* ul)
 {
     hipLaunchKernelGGL(chunk_map_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
                        c.head, c.tiles, nt, c.grp, start, c.cmap);
-    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s);
+    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
 }
 
 // The chunk form's front in one pass:
@@ -1856,7 +2170,7 @@ static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap,
 template <bool HEADERS>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                           const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
-                                          hipStream_t s)
+                                          hipStream_t s, const Utf8Launch* ul)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
     // head | tile totals (nt + 1) | the row-prefix area, whose first nt words hold the states
@@ -1866,25 +2180,40 @@ static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint
                        reinterpret_cast<uint64_t*>(c.head), words);
     hipLaunchKernelGGL(chunk_scan_kernel<HEADERS>, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
                        reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
-    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s);
+    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
 }
 
 // The chunk copy grid and the dense chunks.
 template <bool HEADERS>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                      const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s)
+                                     hipStream_t s, const Utf8Launch* ul)
 {
     const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
     constexpr uint64_t kWaves = kBlock / 64;
     constexpr uint64_t kMaxChunksPerLaunch = ((1ull << 32) / kBlock / 2) * kWaves;
+    const uint32_t dense_blocks = (uint32_t)(chunks / kWaves < 512 ? chunks / kWaves + 1 : 512);
+    if constexpr (!HEADERS) {
+        if (ul) {
+            const Utf8Gather u = launch_utf8_before_copy(*ul, c.head, src, d, start, n, s);
+            for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
+                const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
+                const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
+                hipLaunchKernelGGL(chunk_copy_utf8_kernel, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
+                                   c.tiles + nt, c.head, c.dense, c0, kChunkSplit, u);
+            }
+            hipLaunchKernelGGL(chunk_dense_utf8_kernel, dim3(dense_blocks), dim3(kBlock), 0, s, src, dst, d, n, start,
+                               c.cmap, c.tiles + nt, c.head, c.dense, u);
+            launch_utf8_after_copy(*ul, n, s);
+            return hip_status(hipGetLastError());
+        }
+    }
     for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
         const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
         const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
         hipLaunchKernelGGL(chunk_copy_kernel<HEADERS>, grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start, c.cmap,
                            c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
     }
-    const uint32_t dense_blocks = (uint32_t)(chunks / kWaves < 512 ? chunks / kWaves + 1 : 512);
     hipLaunchKernelGGL(chunk_dense_kernel<HEADERS>, dim3(dense_blocks), dim3(kBlock), 0, s, src, dst, d, flags, n, start,
                        c.cmap, c.tiles + nt, c.head, c.dense);
     return hip_status(hipGetLastError());
@@ -1894,10 +2223,11 @@ static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t 
 // unit copy grid.
 template <bool HEADERS>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s)
+                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
+                                    const Utf8Launch* ul)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
-    if (use_chunks(n, cap)) return launch_chunks<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s);
+    if (use_chunks(n, cap)) return launch_chunks<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
     hipLaunchKernelGGL(prologue_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, n, cap,
                        c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
     // Occupancy: runs of large frames stream faster with 5 blocks per CU (fewer
@@ -1908,6 +2238,19 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
     const uint64_t units = max_units(n, cap);  // upper bound; surplus waves exit at once
     constexpr uint64_t kWavesPerBlock = kBlock / 64;
     constexpr uint64_t kMaxUnitsPerLaunch = ((1ull << 32) / kBlock / 2) * kWavesPerBlock;
+    if constexpr (!HEADERS) {
+        if (ul) {
+            const Utf8Gather u = launch_utf8_before_copy(*ul, c.head, src, d, start, n, s);
+            for (uint64_t u0 = 0; u0 < units; u0 += kMaxUnitsPerLaunch) {
+                const uint64_t nu = units - u0 < kMaxUnitsPerLaunch ? units - u0 : kMaxUnitsPerLaunch;
+                hipLaunchKernelGGL(copy_utf8_kernel, dim3((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock)),
+                                   dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec, c.edge, c.head, u0,
+                                   kCopySplit, u);
+            }
+            launch_utf8_after_copy(*ul, n, s);
+            return hip_status(hipGetLastError());
+        }
+    }
     for (uint64_t u0 = 0; u0 < units; u0 += kMaxUnitsPerLaunch) {
         const uint64_t nu = units - u0 < kMaxUnitsPerLaunch ? units - u0 : kMaxUnitsPerLaunch;
         hipLaunchKernelGGL(copy_kernel<HEADERS>, dim3((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock)),
@@ -1975,6 +2318,75 @@ kmws_status kmws_unpack_gather(const uint8_t* wire, uint64_t wire_len, const uin
                                    n, dst_off, c, s);
     if (st != KMWS_OK) return st;
     return launch_copy_tail<false>(wire, dst, dst_cap, dst_off, out_desc, nullptr, n, c, s);
+}
+
+// ---- gather, unmask and UTF-8 check in one pass over the payload ----
+// The copy's workspace, then the validator's per-frame and per-stream arrays.
+size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
+{
+    return r256(copy_ws_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
+}
+
+// The checks both entries share, in kmws_utf8_validate's order behind the gather's.
+static kmws_status gather_utf8_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, uint64_t dst_cap,
+                                     const uint32_t* stream_first, uint32_t n_streams, size_t workspace_bytes)
+{
+    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
+    if (!ptrs_ok) return KMWS_ERR_INVALID_PARAM;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) return KMWS_ERR_INVALID_PARAM;
+    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
+    if (workspace_bytes < kmws_gather_utf8_workspace_size(n, dst_cap, n_streams)) return KMWS_ERR_BUFFER_TOO_SMALL;
+    if (!utf8_have_device()) return KMWS_ERR_NOT_SUPPORTED;
+    return KMWS_OK;
+}
+
+kmws_status kmws_gather_unmask_utf8(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,
+                                    uint8_t* dst, uint64_t dst_cap, uint64_t* dst_off, const uint32_t* stream_first,
+                                    uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool ptrs = dst_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
+    kmws_status st = gather_utf8_check(ptrs, src, dst, n, dst_cap, stream_first, n_streams, workspace_bytes);
+    if (st != KMWS_OK) return st;
+    CopyWs c;
+    if (!carve(workspace, workspace_bytes, n, dst_cap, c)) return KMWS_ERR_INVALID_PARAM;
+    if (n == 0) {
+        st = launch_copy<false>(src, dst, dst_cap, dst_off, descs, nullptr, 0, c, s);
+        return st != KMWS_OK ? st : launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
+    }
+    // the plain gather has no source span: one the descriptor check never trips on
+    const Utf8Launch ul{static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)), flags, ~0ull, stream_first,
+                        n_streams, carry_in, carry_out, out_utf8};
+    kmws::note_device_batch(2 * dst_cap, s);
+    return launch_copy<false>(src, dst, dst_cap, dst_off, descs, nullptr, n, c, s, &ul);
+}
+
+kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                    int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err, uint8_t* dst,
+                                    uint64_t dst_cap, uint64_t* dst_off, const uint32_t* stream_first,
+                                    uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) return KMWS_ERR_INVALID_PARAM;
+    const bool ptrs = dst_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
+    kmws_status st = gather_utf8_check(ptrs, wire, dst, n, dst_cap, stream_first, n_streams, workspace_bytes);
+    if (st != KMWS_OK) return st;
+    CopyWs c;
+    if (!carve(workspace, workspace_bytes, n, dst_cap, c)) return KMWS_ERR_INVALID_PARAM;
+    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    if (n == 0) {
+        st = launch_zero(dst_off, sizeof(uint64_t), s);
+        return st != KMWS_OK ? st : launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
+    }
+    kmws::note_device_batch(wire_len + dst_cap, s);
+    st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err, c.head}, n,
+                       dst_off, c, s);
+    if (st != KMWS_OK) return st;
+    const Utf8Launch ul{static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)), out_flags, wire_len,
+                        stream_first, n_streams, carry_in, carry_out, out_utf8};
+    return launch_copy_tail<false>(wire, dst, dst_cap, dst_off, out_desc, nullptr, n, c, s, &ul);
 }
 
 // head, then one 64-bit state per 2048-frame tile (pack_headers_chain_kernel)

@@ -31,14 +31,16 @@
 // read once + ~32 B per frame (descriptor, flags, element, verdict).
 // kmws_unmask_utf8_batch / kmws_unpack_unmask_utf8 (below, "the fused in-place
 // pass") run kernels 1-3 and 5 as they are around a payload pass that also
-// unmasks in place.
+// unmasks in place.  kmws_gather_unmask_utf8 / kmws_unpack_gather_utf8
+// (kmws_pack.hip) run them around the gather's copy grid, through the host
+// launchers declared in kmws_utf8_dev.hpp.
 #include "kmws_common.hpp"
 #include "kmws_unmask_tile.hpp"
+#include "kmws_utf8_dev.hpp"
 #include "kmws_utf8_rule.hpp"
 
 namespace kmws {
 
-constexpr uint32_t kUtf8None = 0xFFFFFFFFu;  // first_bad: holds frame + 1 of the BAD frame, 0 = before this batch
 constexpr uint32_t kStatusBadStreams = kStatusBadDesc;  // a malformed stream_first: the same caller error bit
 
 // ---- workspace: the unmask plan's, then the per-frame and per-stream arrays ----
@@ -48,11 +50,12 @@ struct Utf8Ws {
     uint32_t nblk;  // scan blocks of kBlock frames
 };
 static size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
-static Utf8Ws utf8_ws(uint64_t span, uint32_t n, uint32_t n_streams)
+// plan_bytes: what lies in front of the arrays (0: nothing, utf8_frame_arrays_size)
+static Utf8Ws utf8_ws_behind(size_t plan_bytes, uint32_t n, uint32_t n_streams)
 {
     Utf8Ws w;
     w.nblk = (n + kBlock - 1) / kBlock;
-    w.plan_bytes = kmws_unmask_workspace_size(span);
+    w.plan_bytes = plan_bytes;
     w.first_bad = r16(w.plan_bytes);
     w.elems = w.first_bad + r16((size_t)n * 4);
     w.aggs = w.elems + r16((size_t)n * 8);
@@ -60,6 +63,10 @@ static Utf8Ws utf8_ws(uint64_t span, uint32_t n, uint32_t n_streams)
     w.carry = w.pre + r16((size_t)w.nblk * 8);
     w.total = w.carry + r16((size_t)n_streams * 8);
     return w;
+}
+static Utf8Ws utf8_ws(uint64_t span, uint32_t n, uint32_t n_streams)
+{
+    return utf8_ws_behind(kmws_unmask_workspace_size(span), n, n_streams);
 }
 
 // Inclusive scan of one element per lane over the block (Hillis-Steele in LDS);
@@ -215,47 +222,9 @@ __global__ void __launch_bounds__(kBlock) utf8_ctx_kernel(const uint16_t* __rest
     if (i + 1u == stream_end(first, n, s)) carry_tmp[s] = after;
 }
 
-// Byte r (-4 .. 15) of the window: the dword before the word, then the word.
-__device__ __forceinline__ uint32_t window_byte(uint32_t prev, const u32x4& w, int r)
-{
-    const uint32_t dw = r < 0 ? prev : (r < 4 ? w.x : (r < 8 ? w.y : (r < 12 ? w.z : w.w)));
-    return (dw >> (8u * ((uint32_t)r & 3u))) & 0xFFu;
-}
-
-// The bytes of the 16-byte word at address a (w; prev = the dword before it,
-// both unmasked) that belong to the frame [off, end), whose look-back at its
-// first byte is ctx: does the byte rule reject one of them?  The look-back of
-// the word's first byte is the three bytes before it where the frame has them,
-// else ctx and the frame's bytes up to it.
-__device__ __forceinline__ bool word_bad(uint32_t prev, const u32x4& w, uint64_t a, uint64_t off, uint64_t end,
-                                         uint32_t ctx)
-{
-    const bool deep = off + 3u <= a;
-    // the word and its look-back lie inside the frame: four bytes per operation
-    if (deep && end >= a + 16u) return utf8_word_bad_swar(prev, w.x, w.y, w.z, w.w);
-    // a frame edge in or just before the word (rare): a rolled loop, compact code
-    const int s = deep ? -3 : (int)((int64_t)off - (int64_t)a);  // > -3
-    const int e = end >= a + 16u ? 16 : (int)(end - a);
-    uint32_t L = deep ? 0u : (ctx & 0xFFFFFFu);
-    bool bad = false;
-#pragma unroll 1
-    for (int r = s; r < e; ++r) {
-        const uint32_t b = window_byte(prev, w, r);
-        if (r >= 0) bad |= utf8_byte_bad(b, L);
-        L = utf8_append(L, b);
-    }
-    return bad;
-}
-
 constexpr int kUtf8V = (int)(kPlanTile / 16 / kBlock);  // 16-byte words per lane
 constexpr int kUtf8PolLoad = 2;                          // `nt`: the payload is read once
 constexpr int kUtf8RsrcWord3 = 0x00020000;
-
-__device__ __forceinline__ void report_bad(uint32_t* __restrict__ first_bad, uint32_t slot, uint32_t frame)
-{
-    // verdict words only fall: a stale read costs one atomic more, never a verdict
-    if (__builtin_nontemporal_load(&first_bad[slot]) > frame + 1u) atomicMin(&first_bad[slot], frame + 1u);
-}
 
 // Waves per SIMD asked of the register allocator: the read-only stream runs
 // faster with more blocks in flight (all-ASCII 4 GiB: 0.84 ms at 8 waves, 1.17 ms
@@ -516,10 +485,7 @@ __device__ __forceinline__ void fused_lookback(const u32x4 (&v)[kUtf8V], uint32_
 __device__ __forceinline__ bool fused_word_frame_bad(const u32x4& v, uint32_t prev, uint64_t a, uint64_t off,
                                                      uint64_t end, uint32_t r, uint32_t ctx)
 {
-    const u32x4 w = v ^ r;
-    const bool plain = off + 3u <= a && end >= a + 16u && ((w.x | w.y | w.z | w.w) & 0x80808080u) == 0u &&
-                       ((prev ^ r) & 0x80000000u) == 0u;
-    return !plain && word_bad(prev ^ r, w, a, off, end, ctx);
+    return plain_word_frame_bad(v ^ r, prev ^ r, a, off, end, ctx);
 }
 
 // Mask, store and validate a loaded tile.  rec, rec_next, ok, pre: as
@@ -959,6 +925,41 @@ static kmws_status launch_carry_copy(uint32_t n_streams, const kmws_utf8_carry* 
                            n_streams, carry_in, carry_out);
     return hip_status(hipGetLastError());
 }
+
+// ---- for the validating gather (kmws_pack.hip, declared in kmws_utf8_dev.hpp) ----
+size_t utf8_frame_arrays_size(uint32_t n, uint32_t n_streams) { return utf8_ws_behind(0, n, n_streams).total; }
+
+// The arrays stand alone (no plan in front of them); the status word is the caller's.
+static Utf8Arrays frame_arrays(void* arrays, WsHead* head, const Utf8Ws& w)
+{
+    Utf8Arrays a = utf8_arrays(arrays, w);
+    a.head = head;
+    a.map = nullptr;
+    return a;
+}
+Utf8FrameArrays launch_utf8_frame_state(void* arrays, WsHead* head, const uint8_t* base, uint64_t span,
+                                        const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
+                                        const uint32_t* stream_first, uint32_t n_streams,
+                                        const kmws_utf8_carry* carry_in, hipStream_t s)
+{
+    const Utf8Ws w = utf8_ws_behind(0, n, n_streams);
+    const Utf8Arrays a = frame_arrays(arrays, head, w);
+    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, stream_first, n_streams, carry_in, s);
+    return Utf8FrameArrays{a.views, a.first_bad};
+}
+void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                              const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
+                              hipStream_t s)
+{
+    const Utf8Arrays a = frame_arrays(arrays, nullptr, utf8_ws_behind(0, n, n_streams));
+    launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
+}
+kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                   hipStream_t s)
+{
+    return launch_carry_copy(n_streams, carry_in, carry_out, s);
+}
+bool utf8_have_device() { return have_device(); }
 
 // The argument checks the fused entries share with kmws_utf8_validate, in its
 // order; `code`: the schedule to run.
