@@ -86,6 +86,14 @@ kmws_status kmws_resident_guard_counters(int device, uint64_t* unowned_posts, ui
  * through (small jobs, and every job while a device batch of this library
  * runs on the device), or stored into the L2 and released once. */
 kmws_status kmws_resident_store_counters(int device, uint64_t* write_through, uint64_t* released);
+/* The UTF-8 check on the resident worker (kmws_decoder_set_utf8_check):
+ * checked jobs posted on it so far (a withdrawn one is taken off again, as in
+ * kmws_resident_info's jobs), and incarnations of the grid that were asked to
+ * leave because a checked job met the unchecked instantiation of the kernel
+ * (at most one in a process that keeps the check on).  A NULL out-pointer is
+ * skipped; KMWS_ERR_INVALID_PARAM (nothing written) unless 0 <= device <
+ * kmws_device_count(). */
+kmws_status kmws_resident_utf8_counters(int device, uint64_t* checked_jobs, uint64_t* variant_switches);
 /* 1 while device batches enqueued through this library (kmws_unmask_*,
  * kmws_unpack_*, kmws_encode_batch, kmws_gather_unmask) are estimated to run
  * on `device` (20 us + their bytes at 6 TB/s, back to back), else 0. */

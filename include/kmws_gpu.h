@@ -56,6 +56,14 @@ typedef int kmws_status;
  * loop helpers (include/kmws_wshandler.hpp) size their generations to fit. */
 #define KMWS_RESIDENT_MAX_PAYLOADS 128
 #define KMWS_RESIDENT_MAX_BYTES (256u << 10)
+/* The byte limit of a CHECKED job: a call or generation that holds a frame
+ * checked under kmws_decoder_set_utf8_check runs on the grid up to this many
+ * payload bytes and launches above it (the grid validates with one workgroup
+ * per 16 KiB part; above 64 KiB a launch's many small blocks are faster).  The
+ * payload limit is KMWS_RESIDENT_MAX_PAYLOADS as for every job.  The loop
+ * helpers size generations by KMWS_RESIDENT_MAX_BYTES whatever the check: with
+ * it on, a generation between the two limits launches. */
+#define KMWS_RESIDENT_MAX_CHECKED_BYTES (64u << 10)
 
 /* ---- device selection (SURVEY 8 e): which GPU a loop thread's objects use ----
  * kuma runs a pool of event-loop threads (test/client/main.cpp:20,
@@ -202,11 +210,24 @@ void kmws_decoder_set_in_place(kmws_decoder* dec, int on);
  * are checked by the GPU in the pass that unmasks them.  Unmasked frames of a
  * CLIENT-mode decoder, which otherwise need no GPU work, are sent through that
  * pass for the check alone (nothing is stored to them); empty frames never need
- * the GPU.  Cost: a call or generation that holds a checked frame (a text
- * message's frame with payload) is not posted to the resident worker -- the
- * resident grid does not know the rule yet -- but launched, so with the check
- * on text traffic gives up the launch-free path; binary and control-only
- * generations, and everything with the check off, go exactly as before.  If
+ * the GPU.  Routing: a call or generation that holds a checked frame (a text
+ * message's frame with payload) is posted to the calling thread's slot of the
+ * resident worker like any other -- the grid validates in the pass that
+ * unmasks, so text traffic in reads of up to 64 KiB keeps the launch-free
+ * path.  It is launched when it has more than KMWS_RESIDENT_MAX_PAYLOADS
+ * payloads or more than KMWS_RESIDENT_MAX_CHECKED_BYTES (64 KiB) payload bytes
+ * -- a lower byte limit than the KMWS_RESIDENT_MAX_BYTES of a job without a
+ * checked frame -- and, like every job, when the thread's slot is still busy
+ * with its previous job or there is no slot (all taken, or the worker switched
+ * off).  A synchronous feed of one <= 64 KiB read always fits; an RxBatch /
+ * RxLoop generation, which the helpers let grow to 128 KiB and more, launches
+ * once it passes 64 KiB with the check on: flush or submit earlier to stay on
+ * the grid.  The first
+ * checked job of a process on a device also launches if it meets a running
+ * grid: that grid is the kernel without the check and is asked to leave; every
+ * grid after it validates.  Verdicts, bytes and return values are the same
+ * whichever way a job goes.  Binary and control-only generations, and
+ * everything with the check off, go exactly as before.  If
  * the GPU step of a call or generation fails, its frames are dropped as
  * without the check, and the message that was open across them is no longer
  * checkable: its later frames report KMWS_UTF8_NOT_TEXT until the next message
@@ -568,11 +589,10 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  * which an empty FIN frame can do.
  *
  * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
- * checks it); the byte offset of the error; the resident grid does not know the
- * rule (the host path has the check through kmws_decoder_set_utf8_check, and
- * launches the generations that hold a checked frame instead of posting them
- * to the grid).  The in-place unmask and the gather have the check fused into
- * their payload pass: kmws_unmask_utf8_batch and kmws_gather_unmask_utf8 below. */
+ * checks it); the byte offset of the error.  Every payload pass has the check
+ * fused in: the in-place unmask and the gather (kmws_unmask_utf8_batch and
+ * kmws_gather_unmask_utf8 below), and the host path through
+ * kmws_decoder_set_utf8_check -- launched jobs and the resident grid's alike. */
 kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
                                const uint16_t* flags, uint32_t n, int payload_masked,
                                const uint32_t* stream_first, uint32_t n_streams,

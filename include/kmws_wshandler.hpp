@@ -717,8 +717,11 @@ public:
     // without an RxLoop.  Off by default; switch only between messages and
     // while none of this handler's frames are queued.  Advisory: every frame is
     // delivered as before; the application closes with 1007 when
-    // lastFrameUtf8() == KMWS_UTF8_BAD.  With it on, generations that hold text
-    // launch instead of running on the resident worker (include/kmws_gpu.h).
+    // lastFrameUtf8() == KMWS_UTF8_BAD.  With it on, a call or generation that
+    // holds text runs on the resident worker up to
+    // KMWS_RESIDENT_MAX_CHECKED_BYTES (64 KiB) and launches above it; an
+    // RxLoop's generations, cut at KMWS_RESIDENT_MAX_BYTES / 2 pending bytes,
+    // can pass that limit (include/kmws_gpu.h).
     void setUtf8Check(bool on)
     {
         if (st_->dec) kmws_decoder_set_utf8_check(st_->dec, on ? 1 : 0);

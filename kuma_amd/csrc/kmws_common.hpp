@@ -241,6 +241,14 @@ constexpr int kResMaxDescs = KMWS_RESIDENT_MAX_PAYLOADS;
 // asynchronous jobs (an rx / tx batch's submit) alike.
 constexpr uint64_t kResMaxBytes = KMWS_RESIDENT_MAX_BYTES;
 constexpr uint64_t kResMaxBytesAsync = kResMaxBytes;
+// A checked job (kmws_decoder_set_utf8_check) above this many bytes launches:
+// the grid validates with the 16 waves of one workgroup per part, four to a
+// SIMD, and the rule's ALU work no longer hides behind PCIe as it does in a
+// launch's hundreds of small blocks.  Measured, one loop thread, one flush,
+// grid against launch (profiles/p07_resident_utf8.json): 64 KiB (16 x 4 KiB)
+// 21.7-24.7 us against 26.9-30.4 us; 256 KiB (64 x 4 KiB) 64.3-69.1 us against
+// 40.8-41.3 us.  64 KiB is also the most kuma reads at once.
+constexpr uint64_t kResMaxBytesChecked = KMWS_RESIDENT_MAX_CHECKED_BYTES;
 struct ResidentJob {
     int device = -1;
     int slot = -1;
@@ -252,9 +260,30 @@ struct ResidentJob {
 // (nothing posted): too large for one job, no slot free, the thread switched
 // the worker off, its slot still runs a job, or the worker is unusable -- the
 // caller launches instead.
+// check: the job is a checked one (kmws_decoder_set_utf8_check): the grid
+// validates the payloads whose view is checked in the pass that unmasks them,
+// and sets verdict_dv[view.slot] to 1 where the rule rejects a byte -- the
+// contract of launch_unmask_pieces_utf8 above, key 0 included.  views: one per
+// descs[] entry (nullptr: none checked); views2: for the first n_views2 entries
+// of descs2[] (the rest unchecked).  A view whose slot is not below n_verdict is
+// taken as unchecked.  verdict_dv: the device view of n_verdict pinned bytes,
+// zeroed by the caller, which stay valid until the job is done or withdrawn.
+// host_base / host_base2: the host addresses of dev_base / dev_base2 (the words
+// at a part boundary are read there before the post).  KMWS_ERR_NOT_SUPPORTED
+// also while the grid still runs as its unchecked instantiation: it was asked
+// to leave, and the next one validates.
+struct ResidentCheck {
+    const Utf8View* views;
+    const Utf8View* views2;
+    size_t n_views2;
+    uint8_t* verdict_dv;
+    uint32_t n_verdict;
+    const uint8_t* host_base;
+    const uint8_t* host_base2;
+};
 kmws_status resident_post(int device, const kmws_desc* descs, const uint8_t* dev_base, size_t n,
                           const kmws_desc* descs2, const uint8_t* dev_base2, size_t n2, ResidentJob* job,
-                          uint64_t max_bytes = kResMaxBytes);
+                          uint64_t max_bytes = kResMaxBytes, const ResidentCheck* check = nullptr);
 // 1: done; 0: running; KMWS_ERR_NOT_SUPPORTED: withdrawn, never run (launch it).
 int resident_test(const ResidentJob& job);
 // KMWS_OK: done.  KMWS_ERR_NOT_SUPPORTED: withdrawn, never run (launch it).

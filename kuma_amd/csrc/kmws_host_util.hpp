@@ -66,11 +66,15 @@ inline size_t grow(size_t need, size_t have)
 // generation in flight (kmws_decoder.cpp).
 // UTF-8 check (kmws_decoder_set_utf8_check): a descriptor added with
 // add_desc_utf8, or an extra one whose view is checked, makes the job a checked
-// one: it is never posted to the resident worker (the grid does not know the
-// rule) and launches unmask_pieces_utf8_kernel instead, with a view per
-// descriptor, the host-read edge word per piece and one verdict byte per
-// checked frame (utf8_slot / utf8_bad), all in the stage's pinned arrays.  A
-// job without a checked frame goes exactly the way it went before.
+// one, with a view per descriptor and one verdict byte per checked frame
+// (utf8_slot / utf8_bad) in the stage's pinned arrays.  It is posted to the
+// resident worker when it has at most kResMaxDescs payloads and at most
+// kResMaxBytesChecked (64 KiB: below the max_res_bytes of an unchecked job)
+// bytes and the thread has a free and idle slot -- the grid's validating
+// instantiation writes the stage's verdict bytes -- and otherwise, or when the
+// worker withdraws it unrun, launches unmask_pieces_utf8_kernel with the same
+// views, the host-read edge word per piece and the same verdict bytes.  A job
+// without a checked frame goes exactly the way it went before.
 // A stream a batch owns and its stages share; declared first in the batch so
 // it is destroyed after every stage.
 struct BatchStream {
@@ -259,8 +263,9 @@ public:
     // max_res_bytes: the largest job posted on the worker (a synchronous run()
     // keeps kResMaxBytes: one workgroup is slower than a launch's many above it).
     // extra_views: a view per extra descriptor (shorter: the rest unchecked), or
-    // nullptr; a job with a checked frame always launches (the pieces kernel
-    // with the check).
+    // nullptr; a job with a checked frame is posted with its views and the
+    // zeroed verdict bytes if it has at most min(max_res_bytes,
+    // kResMaxBytesChecked) bytes, else launches the pieces kernel with the check.
     kmws_status launch(uint8_t* extra_base = nullptr, uint64_t extra_span = 0,
                        const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr,
                        uint64_t max_res_bytes = kResMaxBytesAsync, const std::vector<Utf8View>* extra_views = nullptr)
@@ -277,14 +282,34 @@ public:
         if (n2 && !extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
         if (n2 && !extra_dv) return KMWS_ERR_INVALID_PARAM;  // must be pinned
         if (n1 && !dv_h_) return KMWS_ERR_FAILED;
-        if (!checked && n1 + n2 <= (size_t)kResMaxDescs) {
+        if (n1 + n2 <= (size_t)kResMaxDescs && (!checked || n_slots_ <= n1 + n2)) {
+            // a checked job: its views, and the stage's verdict bytes zeroed
+            ResidentCheck ck{};
+            if (checked) {
+                const kmws_status es = ensure_host(n1 + n2, 0);
+                if (es != KMWS_OK) return es;
+                views_.resize(n1, Utf8View{0u, 0u});
+                std::memset(h_verdict_, 0, n1 + n2);
+                ck = ResidentCheck{n1 ? views_.data() : nullptr,
+                                   extra_views ? extra_views->data() : nullptr,
+                                   extra_views ? extra_views->size() : 0,
+                                   dv_verdict_,
+                                   n_slots_,
+                                   h_,
+                                   extra_base};
+            }
             const kmws_status st = resident_post(device_, descs_.data(), dv_h_, n1, n2 ? extra->data() : nullptr,
-                                                 extra_dv, n2, &res_, max_res_bytes);
+                                                 extra_dv, n2, &res_,
+                                                 checked ? std::min(max_res_bytes, kResMaxBytesChecked) : max_res_bytes,
+                                                 checked ? &ck : nullptr);
             if (st == KMWS_OK) {  // kept for a launch if the worker withdraws the job
                 saved_base_ = extra_base;
                 saved_span_ = extra_span;
                 saved_dv_ = extra_dv;
                 saved_extra_.assign(extra ? extra->begin() : saved_extra_.end(), extra ? extra->end() : saved_extra_.end());
+                saved_checked_ = checked;
+                saved_views_.clear();
+                if (extra_views) saved_views_ = *extra_views;
                 res_pending_ = true;
                 launched_ = true;
                 return KMWS_OK;
@@ -297,11 +322,15 @@ public:
 private:
     kmws_status launch_saved()
     {
-        return launch_kernels(saved_base_, saved_span_, saved_extra_.empty() ? nullptr : &saved_extra_, saved_dv_);
+        // the call launch() makes, with the job's own check and views
+        return launch_kernels(saved_base_, saved_span_, saved_extra_.empty() ? nullptr : &saved_extra_, saved_dv_,
+                              saved_checked_, saved_checked_ && !saved_views_.empty() ? &saved_views_ : nullptr);
     }
 
     // The device may still write the staging area (a resident job that timed
-    // out): it is left to the device -- never freed, never reused.
+    // out) and, if the job was a checked one, the verdict bytes in the
+    // descriptor allocation: both are left to the device -- never freed,
+    // never reused.
     void abandon()
     {
         h_ = nullptr;
@@ -309,6 +338,13 @@ private:
         cap_ = 0;
         len_ = 0;
         descs_.clear();
+        views_.clear();
+        n_slots_ = 0;
+        h_desc_ = nullptr;
+        dv_desc_ = nullptr;
+        h_view_ = dv_view_ = nullptr;
+        h_verdict_ = dv_verdict_ = nullptr;
+        desc_cap_ = 0;
     }
 
     kmws_status launch_kernels(uint8_t* extra_base, uint64_t extra_span, const std::vector<kmws_desc>* extra,
@@ -495,6 +531,8 @@ private:
     uint64_t saved_span_ = 0;
     uint8_t* saved_dv_ = nullptr;
     std::vector<kmws_desc> saved_extra_;
+    bool saved_checked_ = false;          // ... and its check, with the extra descriptors' views
+    std::vector<Utf8View> saved_views_;
     uint64_t spin_us_ = 1000;
     uint8_t* h_ = nullptr;
     uint8_t* dv_h_ = nullptr;

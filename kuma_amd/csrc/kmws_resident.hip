@@ -44,6 +44,7 @@
 
 #include "kmws_bench.h"
 #include "kmws_host_util.hpp"
+#include "kmws_utf8_dev.hpp"
 
 namespace kmws {
 
@@ -116,6 +117,14 @@ struct ResDesc {  // one payload: device-visible address, bytes, LE key of its f
     uint32_t key;
 };
 static_assert(sizeof(ResDesc) == 16, "ResDesc is one 16-byte load");
+// What a checked job adds (ResSlot::view, ::verdict): per payload its view
+// word and its host address (the edge words are read there), and the device
+// view of the verdict bytes.
+struct ResCheckArgs {
+    uint64_t view[kResMaxDescs];
+    const uint8_t* host[kResMaxDescs];
+    uint64_t verdict;
+};
 
 // The polled word of a slot: job number (bits 0-39), payload count (40-47),
 // parts - 1 (48-49: the workgroups the job is split over), cancelled (61: a
@@ -132,6 +141,11 @@ static_assert(sizeof(ResDesc) == 16, "ResDesc is one 16-byte load");
 constexpr uint64_t kJobMask = (1ull << 40) - 1;
 constexpr int kPartShift = 48;
 constexpr uint64_t kWriteThroughBit = 1ull << 50;  // the job's stores write through (no release)
+// A checked job (kmws_decoder_set_utf8_check): its text payloads are validated
+// in the pass that unmasks them.  Only the validating instantiation of the
+// kernel takes one (ResidentWorker::post); the slot's view words, edge words
+// and the verdict word beside the job word belong to it (ResSlot).
+constexpr uint64_t kCheckBit = 1ull << 51;
 constexpr uint64_t kCancelBit = 1ull << 61;
 constexpr uint64_t kClaimedBit = 1ull << 62;
 constexpr uint64_t kQuitBit = 1ull << 63;
@@ -168,8 +182,22 @@ __host__ __device__ __forceinline__ uint32_t hull_words(uint64_t addr, uint32_t 
 // 128-byte lines.
 struct alignas(256) ResSlot {
     uint64_t word;  // job | ndesc << 40 | (parts - 1) << 48 | cancel << 61 | claimed << 62 | quit << 63
-    uint64_t pad1;
+    // A checked job: the device view of its stage's verdict bytes, tagged with
+    // the job's low 16 bits in bits 48-63 like a descriptor's address.  It
+    // arrives with lane 0's poll of the job word; a stale tag is read again
+    // after the word.
+    uint64_t verdict;
     ResDesc desc[kResMaxDescs];  // desc[i] at 16 + 16 i
+    // A checked job, written by the host before the job word and read after it
+    // was seen, together with the first payload loads (no round trip of their
+    // own).  view[i]: Utf8View::w of payload i (look-back bits 0-23,
+    // kUtf8Checked) | the index of its verdict byte << 32.  edge[p]: the four
+    // bytes before part p's first word as they lay in host memory before the
+    // post, still masked -- part p - 1 may have stored them unmasked by the time
+    // part p runs (PieceRecEdge::edge of the launched kernel); unused where
+    // the part starts on a payload's first word, which takes the view.
+    uint64_t view[kResMaxDescs];
+    uint64_t edge[kResParts];
     alignas(128) uint64_t done[kResParts];  // per part: last job number finished (release: its bytes visible)
     uint64_t gone[kResParts];               // per part: incarnation whose workgroup has left
     alignas(128) uint64_t pad2;
@@ -252,10 +280,27 @@ __device__ __forceinline__ uint64_t ld_agent(const uint64_t* p)
 // workgroups -- runs its words and writes its own done word.  `inc` = this
 // incarnation's number (from 1); `exit_base` = the workgroups of every
 // earlier incarnation (the exit counter's value once they all left).
+//
+// kCheck: the validating instantiation.  It runs unchecked jobs as <false>
+// does and validates the text payloads of a checked one (kCheckBit) on the
+// unmasked words it holds before they leave its registers: the rule of
+// kmws_utf8_dev.hpp on each word, with the dword before the word from the lane
+// below, from the wave below and the stripe before through LDS (s_row, behind
+// one barrier), from the host-read edge word at a part's first word and from
+// the view at a payload's first byte.  A checked part is one round of at most
+// kResBlock * kResWords words -- the host posts no checked job with a larger
+// one (ResidentWorker::post) -- so nothing is carried from round to round.  <false> is the kernel without any of it:
+// a process that never turns the check on runs that one, at its footprint.
+template <bool kCheck>
 __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* mb, ResCtl* ctl, uint64_t inc,
                                                                     uint32_t nslots, uint64_t exit_base,
                                                                     uint64_t idle_ticks, uint64_t lease_ticks)
 {
+    // (kCheck) per payload: its view word; per stripe and wave: the last
+    // unmasked dword of the wave's 64 words; the verdict bytes' address
+    __shared__ uint64_t s_view[kCheck ? kResMaxDescs : 1];
+    __shared__ uint32_t s_row[kResWords][kResBlock / 64];
+    __shared__ uint64_t s_verdict;
     __shared__ ResDesc s_d[kResMaxDescs];
     __shared__ uint32_t s_pre[kResMaxDescs + 1];  // word prefix over the payload hulls
     __shared__ uint64_t s_cmd;
@@ -360,6 +405,14 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                 // payloads (and descriptors) the host wrote before the job word
                 // are read fresh; the other waves load after the barrier below
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+                if constexpr (kCheck) {
+                    // lane 0's second half is the word beside the job word: the
+                    // verdict bytes' address, read again if its tag is stale
+                    if (t == 0 && (cmd & kCheckBit)) {
+                        if ((v1 >> 48) != (cmd & 0xFFFFull)) v1 = ld_sys(pw0 + 1);
+                        s_verdict = v1 & kAddrMask;
+                    }
+                }
             }
             if (t == 0) {
                 s_cmd = cmd;
@@ -406,10 +459,21 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
         const bool wt = (cmd & kWriteThroughBit) != 0;
         // this part's words: an even share, in job order
         const uint32_t wb = (uint32_t)((uint64_t)total * part / parts), we = (uint32_t)((uint64_t)total * (part + 1) / parts);
+        // a checked part is one round with a barrier in it: every wave runs it
+        const bool chk = kCheck && (cmd & kCheckBit) != 0;
         for (uint32_t w0 = wb; w0 < we; w0 += kResBlock * kResWords) {
-            if (w0 + (uint32_t)(t & ~63) >= we) break;  // nothing left for this wave (uniform)
+            if (!chk && w0 + (uint32_t)(t & ~63) >= we) break;  // nothing left for this wave (uniform)
             u32x4 v[kResWords];
             uint32_t di[kResWords];
+            // (checked) the views, one per lane, and this part's edge word:
+            // loads that fly with the payload's
+            uint64_t vw = 0, eg = 0;
+            if constexpr (kCheck) {
+                if (chk) {
+                    if (t < (int)n) vw = ld_sys(&sl->view[t]);
+                    if (t == 0) eg = ld_sys(&sl->edge[part]);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < kResWords; ++i) {
                 // a lane past the part's end loads nothing (clamped to the
@@ -447,7 +511,10 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                 // branched around the descriptor's length and lost the sink
                 // for the last word of a payload on word 0 -- it stored the
                 // whole word, over the next frame's header (r06ap)
-                const bool in = w < we, whole = in & (a >= x.addr) & (a + 16 <= x.addr + x.len);
+                // (a checked job stores nothing to a payload whose key is 0: a
+                // CLIENT-mode decoder's unmasked frames are only validated)
+                const bool in = (w < we) & !(chk & (x.key == 0u)),
+                           whole = in & (a >= x.addr) & (a + 16 <= x.addr + x.len);
                 edge |= (uint32_t)(in & !whole) << i;
                 if (wt) sa[i] = whole ? a : my_sink;
                 else if (whole) *reinterpret_cast<u32x4*>(a) = sv[i];  // into the L2 (the release follows)
@@ -469,6 +536,47 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                     const uint32_t o = dw >> (8 * (b & 3u));
                     if (wt) st_sys1(q, o);
                     else *reinterpret_cast<uint8_t*>(q) = (uint8_t)o;
+                }
+            }
+            if constexpr (kCheck) {
+                if (chk) {  // block-uniform
+                    constexpr int kWaves = kResBlock / 64;
+                    const int lane = t & 63, wave = t >> 6;
+                    uint32_t(*row)[kWaves] = s_row;
+                    if (t < (int)n) s_view[t] = vw;
+                    if (lane == 63) {
+#pragma unroll
+                        for (int i = 0; i < kResWords; ++i) row[i][wave] = sv[i].w;
+                    }
+                    __syncthreads();
+                    // the dword before the part's first word, unmasked: its edge
+                    // word.  Like every look-back below it is used only where it
+                    // belongs to the word's own payload (word_bad): its key phase
+                    // is that word's.
+                    uint32_t first = 0;
+                    if (t == 0) first = (uint32_t)eg ^ rot_key(s_d[di[0]].key, s_d[di[0]].addr);
+#pragma unroll
+                    for (int i = 0; i < kResWords; ++i) {
+                        const uint32_t w = w0 + t + kResBlock * i;
+                        const uint32_t up = __shfl_up(sv[i].w, 1);
+                        uint32_t prev = up;
+                        if (lane == 0) prev = wave ? row[i][wave - 1] : (i ? row[i ? i - 1 : 0][kWaves - 1] : first);
+                        const ResDesc x = s_d[di[i]];
+                        const uint64_t view = s_view[di[i]];
+                        const uint64_t a = ((x.addr >> 4) + (w - s_pre[di[i]])) << 4;
+                        bool bad = false;
+                        if (w < we && (view & kUtf8Checked))
+                            bad = plain_word_frame_bad(sv[i], prev, a, x.addr, x.addr + x.len, (uint32_t)view);
+                        // a rejected byte: the frame's verdict byte, written
+                        // through, by one lane per wave and payload
+                        uint64_t m = __ballot(bad);
+                        while (m) {
+                            const int leader = __ffsll((long long)m) - 1;
+                            const uint32_t ld = (uint32_t)__shfl((int)di[i], leader);
+                            if (lane == leader) st_sys1(s_verdict + (view >> 32), 1u);
+                            m &= ~__ballot(bad && di[i] == ld);
+                        }
+                    }
                 }
             }
         }
@@ -611,11 +719,18 @@ public:
     // calling thread) and returns without waiting; *job = its number.
     // KMWS_ERR_NOT_SUPPORTED: the slot's previous job is still running, or the
     // worker cannot be (re)launched -- nothing was posted.
-    kmws_status post(int b, uint64_t me, const ResDesc* d, uint32_t n, uint64_t* job)
+    // ck: a checked job (its views, verdict bytes and the payloads' host
+    // addresses), which only the validating instantiation takes: from the first
+    // one on every incarnation of this worker is launched as that one, and an
+    // unchecked incarnation it meets is asked to leave (KMWS_ERR_NOT_SUPPORTED:
+    // this caller launches).
+    kmws_status post(int b, uint64_t me, const ResDesc* d, uint32_t n, uint64_t* job, const ResCheckArgs* ck = nullptr)
     {
         if (n == 0 || n > (uint32_t)kResMaxDescs || !usable()) return KMWS_ERR_NOT_SUPPORTED;
         for (uint32_t i = 0; i < n; ++i)
             if ((d[i].addr >> 48) != 0 || d[i].len > kLenMask) return KMWS_ERR_NOT_SUPPORTED;
+        if (ck && (ck->verdict >> 48) != 0) return KMWS_ERR_NOT_SUPPORTED;
+        if (ck && !ld_acq(&checked_seen_)) __atomic_store_n(&checked_seen_, true, __ATOMIC_RELEASE);
         // only the slot's holder writes its descriptors and job word: a post
         // from any other thread is refused (and counted -- never expected)
         if (__atomic_load_n(&hs_[b].owner, __ATOMIC_ACQUIRE) != me) {
@@ -639,10 +754,44 @@ public:
             request_resize(cur);
             return KMWS_ERR_NOT_SUPPORTED;
         }
+        // the incarnation serving is the unchecked instantiation: it leaves as
+        // for a resize, and the relaunch (the next post) is the validating one
+        if (ck && !ld_acq(&inc_checked_)) {
+            if (__atomic_exchange_n(&switch_inc_, cur, __ATOMIC_ACQ_REL) != cur)
+                __atomic_fetch_add(&variant_switches_, 1, __ATOMIC_RELAXED);
+            request_resize(cur);
+            return KMWS_ERR_NOT_SUPPORTED;
+        }
         const uint64_t s = (prev + 1) & kJobMask;
         uint64_t words = 0;
         for (uint32_t i = 0; i < n; ++i) words += hull_words(d[i].addr, d[i].len);
         const uint32_t parts = (uint32_t)std::min<uint64_t>(kResParts, std::max<uint64_t>(1, words / kPartWords));
+        // a checked part is one round of the kernel (no look-back is carried
+        // between rounds): at most kResBlock * kResWords words
+        if (ck && (words + parts - 1) / parts > (uint64_t)(kResBlock * kResWords)) return KMWS_ERR_NOT_SUPPORTED;
+        if (ck) {
+            for (uint32_t i = 0; i < n; ++i) __atomic_store_n(&sl.view[i], ck->view[i], __ATOMIC_RELAXED);
+            // the dword before each later part's first word, read before any
+            // workgroup can have stored it (the device splits at the same words)
+            for (uint32_t p = 1; p < parts; ++p) {
+                const uint64_t wb = words * p / parts;
+                uint64_t pre = 0;
+                uint32_t edge = 0;
+                for (uint32_t i = 0; i < n; ++i) {
+                    const uint64_t hw = hull_words(d[i].addr, d[i].len);
+                    if (wb > pre && wb < pre + hw) {
+                        const uintptr_t first = reinterpret_cast<uintptr_t>(ck->host[i]) & ~(uintptr_t)15;
+                        std::memcpy(&edge, reinterpret_cast<const uint8_t*>(first + 16 * (wb - pre) - 4), 4);
+                    }
+                    pre += hw;
+                }
+                __atomic_store_n(&sl.edge[p], (uint64_t)edge, __ATOMIC_RELAXED);
+            }
+        }
+        // (tagged like a descriptor; once a checked job was seen every job
+        // rewrites it, so a stale one always carries job s - 1's tag)
+        if (ck || ld_acq(&checked_seen_))
+            __atomic_store_n(&sl.verdict, (ck ? ck->verdict : 0ull) | (s & 0xFFFFull) << 48, __ATOMIC_RELAXED);
         const bool wt = words <= (uint64_t)kResWriteThroughWords || device_batch_running(device_);
         __atomic_fetch_add(wt ? &wt_jobs_ : &released_jobs_, 1, __ATOMIC_RELAXED);
         // every polled slot is rewritten, so a stale half always carries job s - 1's tag
@@ -655,9 +804,11 @@ public:
         __atomic_store_n(&hs_[b].parts, parts, __ATOMIC_RELAXED);
         __atomic_store_n(&hs_[b].seq, s, __ATOMIC_RELEASE);
         __atomic_store_n(&hs_[b].jobs, hs_[b].jobs + 1, __ATOMIC_RELAXED);  // (a withdrawn job is taken off again)
+        __atomic_store_n(&hs_[b].checked, ck != nullptr, __ATOMIC_RELAXED);
+        if (ck) __atomic_store_n(&hs_[b].checked_jobs, hs_[b].checked_jobs + 1, __ATOMIC_RELAXED);
         __atomic_store_n(&sl.word,
                          s | (uint64_t)n << 40 | (uint64_t)(parts - 1) << kPartShift | (wt ? kWriteThroughBit : 0) |
-                             kClaimedBit,
+                             (ck ? kCheckBit : 0) | kClaimedBit,
                          __ATOMIC_RELEASE);
         *job = s;
         return KMWS_OK;
@@ -721,6 +872,13 @@ public:
         for (const SlotHost& h : hs_) n += __atomic_load_n(&h.jobs, __ATOMIC_RELAXED);
         return n;
     }
+    uint64_t checked_jobs() const
+    {
+        uint64_t n = 0;
+        for (const SlotHost& h : hs_) n += __atomic_load_n(&h.checked_jobs, __ATOMIC_RELAXED);
+        return n;
+    }
+    uint64_t variant_switches() const { return ld_acq(&variant_switches_); }
     uint64_t launches() const { return ld_acq(&inc_); }
     uint64_t timeouts() const { return ld_acq(&timeouts_); }
     uint64_t withdrawn() const { return ld_acq(&withdrawn_); }
@@ -800,6 +958,7 @@ private:
         __atomic_store_n(&hs_[b].cancelled, s, __ATOMIC_RELEASE);
         __atomic_fetch_add(&withdrawn_, 1, __ATOMIC_RELAXED);
         __atomic_store_n(&hs_[b].jobs, hs_[b].jobs - 1, __ATOMIC_RELAXED);
+        if (__atomic_load_n(&hs_[b].checked, __ATOMIC_RELAXED)) __atomic_store_n(&hs_[b].checked_jobs, hs_[b].checked_jobs - 1, __ATOMIC_RELAXED);
         return true;
     }
 
@@ -935,12 +1094,20 @@ private:
         const uint32_t m = ld_acq(&claimed_);
         const uint32_t nslots = m ? 32u - (uint32_t)__builtin_clz(m) : 1u;
         DevGuard g(device_);
-        hipLaunchKernelGGL(resident_unmask_kernel, dim3(nslots * kResParts), dim3(kResBlock), 0, stream_, dmb_, dctl_,
-                           cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
+        // the instantiation is chosen per incarnation: the validating one from
+        // the first checked job posted on this device on, never before
+        const bool chk = ld_acq(&checked_seen_);
+        if (chk)
+            hipLaunchKernelGGL(resident_unmask_kernel<true>, dim3(nslots * kResParts), dim3(kResBlock), 0, stream_, dmb_,
+                               dctl_, cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
+        else
+            hipLaunchKernelGGL(resident_unmask_kernel<false>, dim3(nslots * kResParts), dim3(kResBlock), 0, stream_, dmb_,
+                               dctl_, cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
         if (hipGetLastError() != hipSuccess) {
             state_ = -1;
             return 0;
         }
+        __atomic_store_n(&inc_checked_, chk, __ATOMIC_RELEASE);
         exit_base_ += (uint64_t)nslots * kResParts;
         __atomic_store_n(&nslots_, nslots, __ATOMIC_RELEASE);
         __atomic_store_n(&inc_, cur + 1, __ATOMIC_RELEASE);
@@ -971,6 +1138,8 @@ private:
         uint64_t jobs = 0;       // jobs posted and not withdrawn (summed by jobs())
         uint64_t owner = 0;      // owner token of the thread holding the slot (0: free)
         uint32_t parts = 0;      // parts of job `seq`
+        bool checked = false;    // job `seq` is a checked one
+        uint64_t checked_jobs = 0;  // checked jobs posted and not withdrawn
     };
     SlotHost hs_[kResSlots];
     alignas(64) uint64_t timeouts_ = 0;
@@ -979,6 +1148,10 @@ private:
     uint64_t wt_jobs_ = 0, released_jobs_ = 0;  // jobs posted by kind (kWriteThroughBit)
     uint64_t late_posts_ = 0;     // jobs asked for after the thread gave its slots back (launched)
     uint64_t drained_ = 0;        // releases that first waited for the slot's last job
+    bool checked_seen_ = false;   // a checked job was posted: incarnations are the validating one from now on
+    bool inc_checked_ = false;    // the latest incarnation is the validating one
+    uint64_t switch_inc_ = 0;     // the last incarnation asked to leave for it
+    uint64_t variant_switches_ = 0;
 };
 
 // Every worker of the process (for the exit handler); never freed.
@@ -1077,26 +1250,43 @@ int thread_slot(int device, ResidentWorker** wout)
 // the calling thread's slot; see kmws_common.hpp.
 kmws_status resident_post(int device, const kmws_desc* descs, const uint8_t* dev_base, size_t n,
                           const kmws_desc* descs2, const uint8_t* dev_base2, size_t n2, ResidentJob* job,
-                          uint64_t max_bytes)
+                          uint64_t max_bytes, const ResidentCheck* check)
 {
     if (n + n2 == 0 || n + n2 > (size_t)kResMaxDescs) return KMWS_ERR_NOT_SUPPORTED;
+    if (check && (!check->verdict_dv || (n && !check->host_base) || (n2 && !check->host_base2)))
+        return KMWS_ERR_INVALID_PARAM;
     ResidentWorker* w = nullptr;
     const int b = thread_slot(device, &w);
     if (b < 0) return KMWS_ERR_NOT_SUPPORTED;
     ResDesc d[kResMaxDescs];
+    ResCheckArgs ck;
+    // a view that is not checked, or whose verdict byte does not exist: only unmasked
+    auto view_word = [&](const Utf8View* v) -> uint64_t {
+        if (!v || !(v->w & kUtf8Checked) || v->slot >= check->n_verdict) return 0ull;
+        return (uint64_t)(v->w & (0xFFFFFFu | kUtf8Checked)) | (uint64_t)v->slot << 32;
+    };
     uint64_t bytes = 0;
     size_t k = 0;
     for (size_t i = 0; i < n; ++i, ++k) {
         d[k] = ResDesc{(uint64_t)(uintptr_t)(dev_base + descs[i].off), descs[i].len, descs[i].key};
         bytes += descs[i].len;
+        if (check) {
+            ck.view[k] = view_word(check->views ? &check->views[i] : nullptr);
+            ck.host[k] = check->host_base + descs[i].off;
+        }
     }
     for (size_t i = 0; i < n2; ++i, ++k) {
         d[k] = ResDesc{(uint64_t)(uintptr_t)(dev_base2 + descs2[i].off), descs2[i].len, descs2[i].key};
         bytes += descs2[i].len;
+        if (check) {
+            ck.view[k] = view_word(check->views2 && i < check->n_views2 ? &check->views2[i] : nullptr);
+            ck.host[k] = check->host_base2 + descs2[i].off;
+        }
     }
     if (bytes > max_bytes || bytes > kResMaxBytesAsync) return KMWS_ERR_NOT_SUPPORTED;
+    if (check) ck.verdict = (uint64_t)(uintptr_t)check->verdict_dv;
     uint64_t s = 0;
-    const kmws_status st = w->post(b, t_slots.token, d, (uint32_t)k, &s);
+    const kmws_status st = w->post(b, t_slots.token, d, (uint32_t)k, &s, check ? &ck : nullptr);
     if (st != KMWS_OK) return st;
     job->device = device;
     job->slot = b;
@@ -1188,6 +1378,16 @@ kmws_status kmws_resident_store_counters(int device, uint64_t* write_through, ui
     if (!w) return KMWS_ERR_INVALID_PARAM;
     if (write_through) *write_through = w->wt_jobs();
     if (released) *released = w->released_jobs();
+    return KMWS_OK;
+}
+
+kmws_status kmws_resident_utf8_counters(int device, uint64_t* checked_jobs, uint64_t* variant_switches)
+{
+    if (device < 0 || device >= kmws::kMaxDevices || kmws_device_count() <= device) return KMWS_ERR_INVALID_PARAM;
+    kmws::ResidentWorker* w = kmws::worker(device);
+    if (!w) return KMWS_ERR_INVALID_PARAM;
+    if (checked_jobs) *checked_jobs = w->checked_jobs();
+    if (variant_switches) *variant_switches = w->variant_switches();
     return KMWS_OK;
 }
 

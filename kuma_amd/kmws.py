@@ -59,6 +59,7 @@ BENCH_EXPORTS = [
     "kmws_check_unmasked", "kmws_resident_enable", "kmws_resident_info", "kmws_resident_counters",
     "kmws_resident_exit_reasons", "kmws_resident_guard_counters", "kmws_device_policy_pick",
     "kmws_device_numa_node", "kmws_resident_store_counters", "kmws_device_batch_busy",
+    "kmws_resident_utf8_counters",
 ]
 
 # unmask schedules (include/kmws_gpu.h KMWS_SCHED_*)
@@ -148,6 +149,7 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_resident_info": (i32, [i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "kmws_resident_exit_reasons": (i32, [i32, C.POINTER(C.c_uint64), i32]),
         "kmws_resident_store_counters": (i32, [i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "kmws_resident_utf8_counters": (i32, [i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "kmws_device_batch_busy": (i32, [i32]),
         "kmws_resident_counters": (i32, [i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint64)]),
@@ -393,6 +395,16 @@ def resident_guard(device: int = 0, L: Optional[C.CDLL] = None) -> dict:
     a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     _check(L.kmws_resident_guard_counters(device, C.byref(a), C.byref(b), C.byref(c)), "kmws_resident_guard_counters")
     return {"unowned_posts": a.value, "late_posts": b.value, "drained_releases": c.value}
+
+
+def resident_utf8(device: int = 0, L: Optional[C.CDLL] = None) -> dict:
+    """kmws_resident_utf8_counters: checked jobs (the UTF-8 check of
+    setUtf8Check) posted on the resident worker, and incarnations of the grid
+    asked to leave for the validating instantiation of its kernel."""
+    L = L or lib()
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _check(L.kmws_resident_utf8_counters(device, C.byref(a), C.byref(b)), "kmws_resident_utf8_counters")
+    return {"checked_jobs": a.value, "variant_switches": b.value}
 
 
 def resident_stores(device: int = 0, L: Optional[C.CDLL] = None) -> dict:
