@@ -164,6 +164,10 @@ inline kmws_status hip_status(hipError_t e)
     return e == hipSuccess ? KMWS_OK : KMWS_ERR_FAILED;
 }
 
+// Workspace carving: sizes rounded up to 16 bytes (a vector word) and to 256.
+inline uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
+inline uint64_t r256(uint64_t x) { return (x + 255) & ~255ull; }
+
 // Zeroes `bytes` (a multiple of 8, at most 4 KiB) at an 8-byte aligned device
 // address with one small kernel.  Used instead of hipMemsetAsync for the status
 // word and scan totals: a call captured into a HIP graph then holds kernel nodes

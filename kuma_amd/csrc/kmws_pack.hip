@@ -2069,8 +2069,6 @@ static uint64_t max_units(uint32_t n, uint64_t cap)
     const uint64_t u = (cap + kUnitWords * 16 - 1) / (kUnitWords * 16) + n + (63ull * n + kUnitWords - 1) / kUnitWords + 1;
     return (u + kBlock / 64 - 1) / (kBlock / 64) * (kBlock / 64);
 }
-static uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
-static uint64_t r256(uint64_t x) { return (x + 255) & ~255ull; }
 
 // head, tile prefixes, row prefixes (the scan's scratch)
 static size_t scan_ws_size(uint32_t n)
@@ -2116,45 +2114,43 @@ static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, CopyWs& c
     return hip_status(hipGetLastError());
 }
 
-// Encode / gather: reduce (row and tile totals), scan the tile totals, the
-// prologue (offsets, edge words, unit records), the copy grid.  Four launches,
-// stream-ordered, nothing on the host in between.
-template <bool HEADERS>
-static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                                    const Utf8Launch* ul = nullptr);
-
-// The chunk form's front: one look-back pass (chunk_scan_kernel) in place of
-// reduce + scan + chunk_map (which the fused unpack-gather keeps: its scan
-// parses the headers).  Same box (profiles/r04aq_chunk_one_pass_ab.txt): cfg4
-// 0.752-0.767 / 0.774-0.779 against 0.749-0.766 / 0.772-0.777, 1-300 B frames
-// 0.35-0.40 / 0.45-0.49 against 0.34-0.39 / 0.44-0.48 (encode / gather).
-template <bool HEADERS>
-static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                          const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
-                                          hipStream_t s, const Utf8Launch* ul = nullptr);
-template <bool HEADERS>
-static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                               const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                               const Utf8Launch* ul = nullptr)
-{
-    if (n == 0) {
-        if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-        return launch_zero(start, sizeof(uint64_t), s);
-    }
-    if (use_chunks(n, cap)) return launch_chunks_one_pass<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
-    const kmws_status st = HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
-                                   : launch_reduce(PayloadSize{d}, n, start, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
-}
-
-// The chunk form after the scan: chunk_map, the chunk copy grid, the dense
-// chunks (usually none: the grid of chunk_dense_kernel exits at once).
+// The chunk form after the scan: the chunk copy grid and the dense chunks
+// (usually none: the grid of chunk_dense_kernel exits at once).  ul: the
+// validating gather (never with HEADERS), whose per-frame kernels run around
+// the copy grid.
 template <bool HEADERS>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                      const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s, const Utf8Launch* ul = nullptr);
+                                     hipStream_t s, const Utf8Launch* ul)
+{
+    const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
+    constexpr uint64_t kWaves = kBlock / 64;
+    constexpr uint64_t kMaxChunksPerLaunch = ((1ull << 32) / kBlock / 2) * kWaves;
+    const dim3 dense_grid((uint32_t)(chunks / kWaves < 512 ? chunks / kWaves + 1 : 512));
+    const Utf8Gather u = ul ? launch_utf8_before_copy(*ul, c.head, src, d, start, n, s) : Utf8Gather{};
+    for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
+        const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
+        const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
+        if (ul)
+            hipLaunchKernelGGL(chunk_copy_utf8_kernel, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
+                               c.tiles + nt, c.head, c.dense, c0, kChunkSplit, u);
+        else
+            hipLaunchKernelGGL(chunk_copy_kernel<HEADERS>, grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
+                               c.cmap, c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
+    }
+    if (ul) {
+        hipLaunchKernelGGL(chunk_dense_utf8_kernel, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
+                           c.tiles + nt, c.head, c.dense, u);
+        launch_utf8_after_copy(*ul, n, s);
+    } else {
+        hipLaunchKernelGGL(chunk_dense_kernel<HEADERS>, dense_grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
+                           c.cmap, c.tiles + nt, c.head, c.dense);
+    }
+    return hip_status(hipGetLastError());
+}
+
+// The chunk form behind reduce + scan (the fused unpack-gather, whose scan
+// parses the headers): chunk_map, then the copy.
 template <bool HEADERS>
 static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
                                  const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
@@ -2165,8 +2161,12 @@ static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap,
     return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
 }
 
-// The chunk form's front in one pass:
-// zero the head, the totals and the tile states, then chunk_scan_kernel.
+// The chunk form's front in one pass: one look-back pass (chunk_scan_kernel)
+// in place of reduce + scan + chunk_map -- zero the head, the totals and the
+// tile states, then chunk_scan_kernel.  Same box
+// (profiles/r04aq_chunk_one_pass_ab.txt): cfg4 0.752-0.767 / 0.774-0.779
+// against 0.749-0.766 / 0.772-0.777, 1-300 B frames 0.35-0.40 / 0.45-0.49
+// against 0.34-0.39 / 0.44-0.48 (encode / gather).
 template <bool HEADERS>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                           const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
@@ -2183,48 +2183,12 @@ static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint
     return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
 }
 
-// The chunk copy grid and the dense chunks.
-template <bool HEADERS>
-static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                     const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s, const Utf8Launch* ul)
-{
-    const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
-    constexpr uint64_t kWaves = kBlock / 64;
-    constexpr uint64_t kMaxChunksPerLaunch = ((1ull << 32) / kBlock / 2) * kWaves;
-    const uint32_t dense_blocks = (uint32_t)(chunks / kWaves < 512 ? chunks / kWaves + 1 : 512);
-    if constexpr (!HEADERS) {
-        if (ul) {
-            const Utf8Gather u = launch_utf8_before_copy(*ul, c.head, src, d, start, n, s);
-            for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
-                const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
-                const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
-                hipLaunchKernelGGL(chunk_copy_utf8_kernel, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
-                                   c.tiles + nt, c.head, c.dense, c0, kChunkSplit, u);
-            }
-            hipLaunchKernelGGL(chunk_dense_utf8_kernel, dim3(dense_blocks), dim3(kBlock), 0, s, src, dst, d, n, start,
-                               c.cmap, c.tiles + nt, c.head, c.dense, u);
-            launch_utf8_after_copy(*ul, n, s);
-            return hip_status(hipGetLastError());
-        }
-    }
-    for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
-        const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
-        const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
-        hipLaunchKernelGGL(chunk_copy_kernel<HEADERS>, grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start, c.cmap,
-                           c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
-    }
-    hipLaunchKernelGGL(chunk_dense_kernel<HEADERS>, dim3(dense_blocks), dim3(kBlock), 0, s, src, dst, d, flags, n, start,
-                       c.cmap, c.tiles + nt, c.head, c.dense);
-    return hip_status(hipGetLastError());
-}
-
 // The copy form after the scan: chunks (small mean) or the prologue and the
 // unit copy grid.
 template <bool HEADERS>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                     const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                                    const Utf8Launch* ul)
+                                    const Utf8Launch* ul = nullptr)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
     if (use_chunks(n, cap)) return launch_chunks<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
@@ -2238,25 +2202,38 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
     const uint64_t units = max_units(n, cap);  // upper bound; surplus waves exit at once
     constexpr uint64_t kWavesPerBlock = kBlock / 64;
     constexpr uint64_t kMaxUnitsPerLaunch = ((1ull << 32) / kBlock / 2) * kWavesPerBlock;
-    if constexpr (!HEADERS) {
-        if (ul) {
-            const Utf8Gather u = launch_utf8_before_copy(*ul, c.head, src, d, start, n, s);
-            for (uint64_t u0 = 0; u0 < units; u0 += kMaxUnitsPerLaunch) {
-                const uint64_t nu = units - u0 < kMaxUnitsPerLaunch ? units - u0 : kMaxUnitsPerLaunch;
-                hipLaunchKernelGGL(copy_utf8_kernel, dim3((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock)),
-                                   dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec, c.edge, c.head, u0,
-                                   kCopySplit, u);
-            }
-            launch_utf8_after_copy(*ul, n, s);
-            return hip_status(hipGetLastError());
-        }
-    }
+    const Utf8Gather u = ul ? launch_utf8_before_copy(*ul, c.head, src, d, start, n, s) : Utf8Gather{};
     for (uint64_t u0 = 0; u0 < units; u0 += kMaxUnitsPerLaunch) {
         const uint64_t nu = units - u0 < kMaxUnitsPerLaunch ? units - u0 : kMaxUnitsPerLaunch;
-        hipLaunchKernelGGL(copy_kernel<HEADERS>, dim3((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec, c.edge, c.head, u0, kCopySplit);
+        const dim3 grid((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock));
+        if (ul)
+            hipLaunchKernelGGL(copy_utf8_kernel, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec, c.edge,
+                               c.head, u0, kCopySplit, u);
+        else
+            hipLaunchKernelGGL(copy_kernel<HEADERS>, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec,
+                               c.edge, c.head, u0, kCopySplit);
     }
+    if (ul) launch_utf8_after_copy(*ul, n, s);
     return hip_status(hipGetLastError());
+}
+
+// Encode / gather: reduce (row and tile totals), scan the tile totals, the
+// prologue (offsets, edge words, unit records), the copy grid.  Four launches,
+// stream-ordered, nothing on the host in between.
+template <bool HEADERS>
+static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
+                               const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
+                               const Utf8Launch* ul = nullptr)
+{
+    if (n == 0) {
+        if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+        return launch_zero(start, sizeof(uint64_t), s);
+    }
+    if (use_chunks(n, cap)) return launch_chunks_one_pass<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
+    const kmws_status st = HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
+                                   : launch_reduce(PayloadSize{d}, n, start, c, s);
+    if (st != KMWS_OK) return st;
+    return launch_copy_tail<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
 }
 
 }  // namespace kmws
@@ -2327,17 +2304,14 @@ size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_
     return r256(copy_ws_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
 }
 
-// The checks both entries share, in kmws_utf8_validate's order behind the gather's.
+// The checks both entries share: the gather's pointers whatever n is, then the
+// stream arguments and the workspace (utf8_stream_args_check).
 static kmws_status gather_utf8_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, uint64_t dst_cap,
                                      const uint32_t* stream_first, uint32_t n_streams, size_t workspace_bytes)
 {
-    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
     if (!ptrs_ok) return KMWS_ERR_INVALID_PARAM;
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) return KMWS_ERR_INVALID_PARAM;
-    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
-    if (workspace_bytes < kmws_gather_utf8_workspace_size(n, dst_cap, n_streams)) return KMWS_ERR_BUFFER_TOO_SMALL;
-    if (!utf8_have_device()) return KMWS_ERR_NOT_SUPPORTED;
-    return KMWS_OK;
+    return utf8_stream_args_check(true, a, b, n, stream_first, n_streams,
+                                  kmws_gather_utf8_workspace_size(n, dst_cap, n_streams), workspace_bytes);
 }
 
 kmws_status kmws_gather_unmask_utf8(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,

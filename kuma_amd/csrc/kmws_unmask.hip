@@ -151,7 +151,6 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
                                             uint64_t* s_end, uint32_t* s_key, const u32x4* pre = nullptr,
                                             uint64_t* stamps = nullptr)
 {
-    using Cfg = UnmaskCfg<V>;
     constexpr int SP = !NT ? kPolPlain : (TWO ? kPolStreamStoreLarge : kPolStreamStoreSmall);  // TWO: the capped launches
     const int tid = threadIdx.x;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);
@@ -175,7 +174,7 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
 
     // frames [f, flast] are the only ones that can overlap the tile: flast's
     // region holds the next tile's start (the map's last entry is a sentinel)
-    uint32_t f = tile_rec_frame(rec, n);
+    const uint32_t f = tile_rec_frame(rec, n);
     const uint32_t flast = tile_rec_frame(rec_next, n);
     const kmws_desc d0 = d[f < n ? f : 0];
 
@@ -192,31 +191,8 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
     // gaps) are not stored.
     if (TWO && FULL && flast <= f + 1 && f < n) {
         const kmws_desc d1 = flast > f && flast < n ? d[flast] : kmws_desc{~0ull, 0u, 0u};
-        const uint32_t r0 = rot_key(d0.key, d0.off), r1 = rot_key(d1.key, d1.off);
-        // payload extents relative to the tile, clamped to [0, kTile]: block-uniform
-        // scalars, so each per-word test is one 32-bit compare
-        constexpr uint32_t T = (uint32_t)Cfg::kTile;
-        auto rel = [&](uint64_t x) -> uint32_t {
-            return x <= tile_lo ? 0u : (x - tile_lo >= T ? T : (uint32_t)(x - tile_lo));
-        };
-        const uint32_t s0 = rel(d0.off), t0 = rel(d0.off + d0.len);
-        const uint32_t s1 = rel(d1.off), t1 = d1.len ? rel(d1.off + d1.len) : s1;
         u32x4 m[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
-            u32x4 mm = u32x4{0, 0, 0, 0};
-            if (s0 <= x && t0 >= x + 16) {
-                mm = u32x4{r0, r0, r0, r0};
-            } else if (s1 <= x && t1 >= x + 16) {
-                mm = u32x4{r1, r1, r1, r1};
-            } else {  // a word holding a frame edge: byte-exact
-                // each frame's bytes of the word, clamped to [0, 16] (empty if none)
-                auto cl = [&](uint32_t y) -> int { return y <= x ? 0 : (y - x >= 16u ? 16 : (int)(y - x)); };
-                mm = (word_byte_range(cl(s0), cl(t0)) & r0) | (word_byte_range(cl(s1), cl(t1)) & r1);
-            }
-            m[i] = mm;
-        }
+        two_frame_masks(tile_lo, d0, d1, tid, m);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
@@ -227,63 +203,11 @@ __device__ __forceinline__ void finish_tile(uint8_t* __restrict__ base, uint64_t
         return;
     }
 
-    // General path: stage the descriptors of frames overlapping the tile in
-    // LDS, kCap per round, and build a byte-exact mask per 16-byte word.
+    // General path: the descriptors of the frames overlapping the tile staged
+    // in LDS, a byte-exact mask per 16-byte word (staged_masks; the first
+    // round's descriptors may have been issued before the payload loads: `pre`).
     u32x4 m[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) m[i] = u32x4{0, 0, 0, 0};
-    // One round: lane tid holds descriptor f + tid (`have`: it exists and can
-    // overlap the tile); returns how many were staged.
-    auto round = [&](bool have, const u32x4& x) -> int {
-        int valid = 0;
-        if (have) {
-            const uint64_t off = (uint64_t)x.x | ((uint64_t)x.y << 32);
-            if (off < tile_hi) {
-                valid = 1;
-                s_off[tid] = off;
-                s_end[tid] = off + x.z;
-                s_key[tid] = x.w;
-            }
-        }
-        const int cnt = __syncthreads_count(valid);  // sorted => a prefix
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-            int lo = 0, hi = cnt;  // first staged frame with end > a
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_end[mid] <= a) lo = mid + 1; else hi = mid;
-            }
-            for (int j = lo; j < cnt; ++j) {
-                const uint64_t o = s_off[j];
-                if (o >= a + 16) break;
-                const uint64_t e = s_end[j];
-                const uint32_t r = rot_key(s_key[j], o);
-                if (o <= a && e >= a + 16) {
-                    m[i] |= u32x4{r, r, r, r};
-                } else {
-                    const int blo = o > a ? (int)(o - a) : 0;
-                    const int bhi = e < a + 16 ? (int)(e - a) : 16;
-                    m[i].x |= r & dword_byte_mask(blo, bhi, 0);
-                    m[i].y |= r & dword_byte_mask(blo, bhi, 1);
-                    m[i].z |= r & dword_byte_mask(blo, bhi, 2);
-                    m[i].w |= r & dword_byte_mask(blo, bhi, 3);
-                }
-            }
-        }
-        __syncthreads();  // every lane done reading this round's LDS (also before a next tile reuses it)
-        return cnt;
-    };
-    // no descriptor loads past the tile's last frame; the first round's may
-    // have been issued before the payload loads (`pre`): then no wait here
-    // covers the payload
-    auto have_f = [&]() { return f + (uint32_t)tid < n && f + (uint32_t)tid <= flast; };
-    auto load_f = [&]() { return have_f() ? *reinterpret_cast<const u32x4*>(d + f + tid) : u32x4{0, 0, 0, 0}; };
-    int cnt = pre ? round(have_f(), *pre) : round(have_f(), load_f());
-    while (cnt == Cfg::kCap) {
-        f += Cfg::kCap;
-        cnt = round(have_f(), load_f());
-    }
+    staged_masks(tile_lo, tile_hi, d, n, f, flast, pre, s_off, s_end, s_key, tid, m);
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
@@ -436,33 +360,10 @@ __global__ void __launch_bounds__(kBlock) unmask_pieces_kernel(uint8_t* __restri
     constexpr int V = kPieceWords / kBlock;
     const PieceRec pr = pieces[blockIdx.x];
     const kmws_desc x = d[pr.frame];
-    const uint64_t end = x.off + x.len;
-    const uint64_t w0 = (x.off >> 4) + (uint64_t)pr.piece * kPieceWords;
-    const uint64_t wh = (end + 15) >> 4;
-    const uint64_t w1 = wh < w0 + kPieceWords ? wh : w0 + kPieceWords;
-    const uint32_t r = rot_key(x.key, x.off);
+    const PieceHull h = piece_hull(x, pr.piece);
     u32x4 v[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
-        v[i] = w < w1 ? *reinterpret_cast<const u32x4*>(base + 16 * w) : u32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
-        if (w >= w1) continue;
-        const uint64_t a = 16 * w;
-        if (a >= x.off && a + 16 <= end) {
-            *reinterpret_cast<u32x4*>(base + a) = v[i] ^ r;
-        } else {  // the hull's first or last word: own bytes only
-            const uint64_t lo = a > x.off ? a : x.off, hi = a + 16 < end ? a + 16 : end;
-            for (uint64_t q = lo; q < hi; ++q) {
-                const uint32_t b = (uint32_t)(q - a);
-                const uint32_t dw = (b & 8u) ? ((b & 4u) ? v[i].w : v[i].z) : ((b & 4u) ? v[i].y : v[i].x);
-                base[q] = (uint8_t)((dw ^ r) >> (8 * (b & 3u)));
-            }
-        }
-    }
+    load_piece(base, h, v);
+    store_piece(base, x, h, v);
 }
 
 // ---- synthetic fill: byte i = byte (i & 7) of splitmix64(seed + (i >> 3)) ----
@@ -671,26 +572,12 @@ static kmws_status launch_apply(uint32_t code, uint8_t* base, uint64_t span, con
     const TileRec* map = reinterpret_cast<const TileRec*>(head + 1);
     const uint64_t nfull = span / ProdCfg::kTile;
     const bool temporal = temporal_stores(code);
-    // a launch may hold at most 2^32 work-items: huge spans go in pieces of blocks
-    constexpr uint64_t kMaxBlocks = (1ull << 32) / kBlock / 2;
     const unsigned lds_pad = unmask_lds_pad(span, n);
     const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
-    for (uint64_t b0 = 0; b0 < nfull; b0 += kMaxBlocks) {
-        const dim3 grid((uint32_t)(nfull - b0 < kMaxBlocks ? nfull - b0 : kMaxBlocks));
-        const uint32_t bb = (uint32_t)b0;
-        if (lds_pad && !temporal)
-            hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, true, true>), grid, dim3(kBlock), lds_pad, s, base, descs,
-                               n, map, head, tm, bb);
-        else if (lds_pad)
-            hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, true, false>), grid, dim3(kBlock), lds_pad, s, base,
-                               descs, n, map, head, tm, bb);
-        else if (!temporal)
-            hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, false, true>), grid, dim3(kBlock), 0, s, base, descs, n,
-                               map, head, tm, bb);
-        else
-            hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, false, false>), grid, dim3(kBlock), 0, s, base, descs,
-                               n, map, head, tm, bb);
-    }
+    launch_split_grid(nfull, lds_pad, temporal, [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
+        hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, decltype(two)::value, decltype(nt)::value>), grid,
+                           dim3(kBlock), pad, s, base, descs, n, map, head, tm, b0);
+    });
     if (ntiles > nfull)  // the partial last tile
         hipLaunchKernelGGL(unmask_tail_kernel<kUnmaskV>, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, map, head,
                            (uint32_t)nfull);

@@ -49,7 +49,6 @@ struct Utf8Ws {
     size_t first_bad, elems, aggs, pre, carry, total;
     uint32_t nblk;  // scan blocks of kBlock frames
 };
-static size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 // plan_bytes: what lies in front of the arrays (0: nothing, utf8_frame_arrays_size)
 static Utf8Ws utf8_ws_behind(size_t plan_bytes, uint32_t n, uint32_t n_streams)
 {
@@ -226,6 +225,73 @@ constexpr int kUtf8V = (int)(kPlanTile / 16 / kBlock);  // 16-byte words per lan
 constexpr int kUtf8PolLoad = 2;                          // `nt`: the payload is read once
 constexpr int kUtf8RsrcWord3 = 0x00020000;
 
+// ---- the checks of a loaded tile: the validator's and the fused pass's ----
+// v[i]: the lane's word at lo + 16 (tid + kBlock i), prev[i]: the dword before
+// it, both as they lie in memory.
+//
+// One frame f (d0, view fv, rotated key r; 0: a plain payload) covers the tile,
+// block-uniform: a word of ASCII bytes after an ASCII byte is decided by one OR
+// and a test, and a wave that holds no other word skips the rule.
+__device__ __forceinline__ void covered_tile_check(const u32x4 (&v)[kUtf8V], const uint32_t (&prev)[kUtf8V],
+                                                   uint32_t r, uint64_t lo, const kmws_desc& d0, Utf8View fv,
+                                                   uint32_t f, uint32_t* __restrict__ first_bad)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint64_t end = d0.off + d0.len;
+    bool slow[kUtf8V];
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < kUtf8V; ++i) {
+        const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
+        const u32x4 w = v[i] ^ r;
+        const uint32_t hb = (w.x | w.y | w.z | w.w) & 0x80808080u;
+        slow[i] = hb != 0u || ((prev[i] ^ r) & 0x80000000u) != 0u || a < d0.off + 3u;
+        any |= slow[i];
+    }
+    bool bad = false;
+    if (__any(any)) {
+#pragma unroll
+        for (int i = 0; i < kUtf8V; ++i) {
+            const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
+            if (slow[i]) bad |= word_bad(prev[i] ^ r, v[i] ^ r, a, d0.off, end, fv.w);
+        }
+    }
+    const unsigned long long m = __ballot(bad);  // one report per wave
+    if (m != 0ull && lane == __ffsll((long long)m) - 1) report_bad(first_bad, fv.slot, f);
+}
+
+// Several frames (or a frame edge) in the tile: each of the lane's words below
+// hi finds its frames in the sorted descriptors [f, fl] and is checked against
+// every checked one.  MASKED: the payload is still masked with the frames' keys.
+template <bool MASKED>
+__device__ __forceinline__ void frames_check(const u32x4 (&v)[kUtf8V], const uint32_t (&prev)[kUtf8V], uint64_t lo,
+                                             uint64_t hi, const kmws_desc* __restrict__ d, uint32_t f, uint32_t fl,
+                                             const Utf8View* __restrict__ views, uint32_t* __restrict__ first_bad)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < kUtf8V; ++i) {
+        const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
+        if (a >= hi) continue;
+        uint32_t gl = f, gh = fl + 1u;  // the first frame that ends after a
+        while (gl < gh) {
+            const uint32_t mid = gl + (gh - gl) / 2;
+            const kmws_desc dm = d[mid];
+            if (dm.off + dm.len <= a) gl = mid + 1; else gh = mid;
+        }
+        for (uint32_t g = gl; g <= fl; ++g) {
+            const kmws_desc dg = d[g];
+            if (dg.off >= a + 16u) break;
+            if (dg.len == 0u) continue;
+            const Utf8View gv = views[g];
+            if (!(gv.w & kUtf8Checked)) continue;
+            const uint32_t r = MASKED ? rot_key(dg.key, dg.off) : 0u;
+            if (plain_word_frame_bad(v[i] ^ r, prev[i] ^ r, a, dg.off, dg.off + dg.len, gv.w))
+                report_bad(first_bad, gv.slot, g);
+        }
+    }
+}
+
 // Waves per SIMD asked of the register allocator: the read-only stream runs
 // faster with more blocks in flight (all-ASCII 4 GiB: 0.84 ms at 8 waves, 1.17 ms
 // at 5), and the word form's class masks are what costs registers.  7 fits the
@@ -290,59 +356,12 @@ __global__ void __launch_bounds__(kBlock, MASKED ? 4 : 7) utf8_payload_kernel(co
     }
 
     if (cov) {
-        // One frame covers the tile (block-uniform): a word of ASCII bytes after
-        // an ASCII byte is decided by one OR and a test.
-        const uint32_t r = MASKED ? recs.at.rkey : 0u;
-        const uint64_t end = d0.off + d0.len;
-        bool slow[kUtf8V];
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < kUtf8V; ++i) {
-            const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
-            const u32x4 w = v[i] ^ r;
-            const uint32_t hb = (w.x | w.y | w.z | w.w) & 0x80808080u;
-            slow[i] = hb != 0u || ((prev[i] ^ r) & 0x80000000u) != 0u || a < d0.off + 3u;
-            any |= slow[i];
-        }
-        bool bad = false;
-        if (__any(any)) {
-#pragma unroll
-            for (int i = 0; i < kUtf8V; ++i) {
-                const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
-                if (slow[i]) bad |= word_bad(prev[i] ^ r, v[i] ^ r, a, d0.off, end, fv.w);
-            }
-        }
-        const unsigned long long m = __ballot(bad);  // one report per wave
-        if (m != 0ull && lane == __ffsll((long long)m) - 1) report_bad(first_bad, fv.slot, f);
+        covered_tile_check(v, prev, MASKED ? recs.at.rkey : 0u, lo, d0, fv, f, first_bad);
         return;
     }
 
-    // Several frames (or a frame edge) in the tile: each word finds its frames
-    // in the sorted descriptors [f, fl].
-#pragma unroll
-    for (int i = 0; i < kUtf8V; ++i) {
-        const uint64_t a = lo + 16u * (uint64_t)(tid + kBlock * i);
-        if (a >= hi) continue;
-        uint32_t gl = f, gh = fl + 1u;  // the first frame that ends after a
-        while (gl < gh) {
-            const uint32_t mid = gl + (gh - gl) / 2;
-            const kmws_desc dm = d[mid];
-            if (dm.off + dm.len <= a) gl = mid + 1; else gh = mid;
-        }
-        for (uint32_t g = gl; g <= fl; ++g) {
-            const kmws_desc dg = d[g];
-            if (dg.off >= a + 16u) break;
-            if (dg.len == 0u) continue;
-            const Utf8View gv = views[g];
-            if (!(gv.w & kUtf8Checked)) continue;
-            const uint32_t r = MASKED ? rot_key(dg.key, dg.off) : 0u;
-            const uint64_t end = dg.off + dg.len;
-            const u32x4 w = v[i] ^ r;
-            const bool plain = dg.off + 3u <= a && end >= a + 16u && ((w.x | w.y | w.z | w.w) & 0x80808080u) == 0u &&
-                               ((prev[i] ^ r) & 0x80000000u) == 0u;
-            if (!plain && word_bad(prev[i] ^ r, w, a, dg.off, end, gv.w)) report_bad(first_bad, gv.slot, g);
-        }
-    }
+    // Several frames (or a frame edge) in the tile.
+    frames_check<MASKED>(v, prev, lo, hi, d, f, fl, views, first_bad);
 }
 
 __global__ void __launch_bounds__(kBlock) utf8_finish_kernel(uint32_t n, const uint32_t* __restrict__ first,
@@ -489,8 +508,9 @@ __device__ __forceinline__ bool fused_word_frame_bad(const u32x4& v, uint32_t pr
 }
 
 // Mask, store and validate a loaded tile.  rec, rec_next, ok, pre: as
-// finish_tile (kmws_unmask.hip) takes them, and the same three mask paths and
-// store policies; edge: see fused_lookback.
+// finish_tile (kmws_unmask.hip) takes them; the masks are the apply's own
+// (the record's key, two_frame_masks, staged_masks: kmws_unmask_tile.hpp) and
+// so are the store policies; edge: see fused_lookback.
 template <bool FULL, bool TWO, bool NT>
 __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t tile_lo, uint64_t tile_hi,
                                            const kmws_desc* __restrict__ d, uint32_t n, TileRec rec, TileRec rec_next,
@@ -502,7 +522,7 @@ __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t 
     constexpr int V = kUtf8V;
     using Cfg = UnmaskCfg<V>;
     constexpr int SP = !NT ? kPolPlain : (TWO ? kPolStreamStoreLarge : kPolStreamStoreSmall);
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, tile_lo, tile_hi);
 
     // One frame covers the tile: the record holds the whole mask.  No
@@ -537,30 +557,9 @@ __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t 
         // block-uniform: binary, RSV1 and control tiles end here (a covering
         // frame is never empty and never starts past the tile's first byte)
         if (!ok | (f >= n) | !(fv.w & kUtf8Checked) | (d0.len == 0u) | (d0.off > tile_lo)) return;
-        const uint64_t end = d0.off + d0.len;
         uint32_t prev[V];
         fused_lookback(v, edge, s_row, prev);
-        // a word of ASCII bytes after an ASCII byte is decided by one OR and a test
-        bool slow[V];
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-            const u32x4 w = v[i] ^ r;
-            const uint32_t hb = (w.x | w.y | w.z | w.w) & 0x80808080u;
-            slow[i] = hb != 0u || ((prev[i] ^ r) & 0x80000000u) != 0u || a < d0.off + 3u;
-            any |= slow[i];
-        }
-        bool bad = false;
-        if (__any(any)) {
-#pragma unroll
-            for (int i = 0; i < V; ++i) {
-                const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-                if (slow[i]) bad |= word_bad(prev[i] ^ r, v[i] ^ r, a, d0.off, end, fv.w);
-            }
-        }
-        const unsigned long long m = __ballot(bad);  // one report per wave
-        if (m != 0ull && lane == __ffsll((long long)m) - 1) report_bad(first_bad, fv.slot, f);
+        covered_tile_check(v, prev, r, tile_lo, d0, fv, f, first_bad);
         return;
     }
 
@@ -574,28 +573,8 @@ __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t 
     if (TWO && FULL && flast <= f0 + 1 && f0 < n) {
         const bool two = flast > f0 && flast < n;
         const kmws_desc d1 = two ? d[flast] : kmws_desc{~0ull, 0u, 0u};
-        const uint32_t r0 = rot_key(d0.key, d0.off), r1 = rot_key(d1.key, d1.off);
-        constexpr uint32_t T = (uint32_t)Cfg::kTile;
-        auto rel = [&](uint64_t x) -> uint32_t {
-            return x <= tile_lo ? 0u : (x - tile_lo >= T ? T : (uint32_t)(x - tile_lo));
-        };
-        const uint32_t s0 = rel(d0.off), t0 = rel(d0.off + d0.len);
-        const uint32_t s1 = rel(d1.off), t1 = d1.len ? rel(d1.off + d1.len) : s1;
         u32x4 m[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint32_t x = 16u * (uint32_t)(tid + kBlock * i);
-            u32x4 mm = u32x4{0, 0, 0, 0};
-            if (s0 <= x && t0 >= x + 16) {
-                mm = u32x4{r0, r0, r0, r0};
-            } else if (s1 <= x && t1 >= x + 16) {
-                mm = u32x4{r1, r1, r1, r1};
-            } else {  // a word holding a frame edge: byte-exact
-                auto cl = [&](uint32_t y) -> int { return y <= x ? 0 : (y - x >= 16u ? 16 : (int)(y - x)); };
-                mm = (word_byte_range(cl(s0), cl(t0)) & r0) | (word_byte_range(cl(s1), cl(t1)) & r1);
-            }
-            m[i] = mm;
-        }
+        const auto [r0, r1, s0, t0, s1, t1] = two_frame_masks(tile_lo, d0, d1, tid, m);
         // the two views: scalar loads beside the descriptors', used after the stores
         const Utf8View v0 = views[f0];
         const Utf8View v1 = two ? views[flast] : Utf8View{0u, 0u};
@@ -625,60 +604,10 @@ __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t 
     }
 
     // General path: the descriptors of the frames overlapping the tile staged
-    // in LDS, kCap per round, a byte-exact mask per 16-byte word.
+    // in LDS, a byte-exact mask per 16-byte word.
     u32x4 m[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) m[i] = u32x4{0, 0, 0, 0};
-    uint32_t f = f0;
-    auto round = [&](bool have, const u32x4& x) -> int {
-        int valid = 0;
-        if (have) {
-            const uint64_t off = (uint64_t)x.x | ((uint64_t)x.y << 32);
-            if (off < tile_hi) {
-                valid = 1;
-                s_off[tid] = off;
-                s_end[tid] = off + x.z;
-                s_key[tid] = x.w;
-            }
-        }
-        const int cnt = __syncthreads_count(valid);  // sorted => a prefix
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-            int lo = 0, hi = cnt;  // first staged frame with end > a
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_end[mid] <= a) lo = mid + 1; else hi = mid;
-            }
-            for (int j = lo; j < cnt; ++j) {
-                const uint64_t o = s_off[j];
-                if (o >= a + 16) break;
-                const uint64_t e = s_end[j];
-                const uint32_t r = rot_key(s_key[j], o);
-                if (o <= a && e >= a + 16) {
-                    m[i] |= u32x4{r, r, r, r};
-                } else {
-                    const int blo = o > a ? (int)(o - a) : 0;
-                    const int bhi = e < a + 16 ? (int)(e - a) : 16;
-                    m[i].x |= r & dword_byte_mask(blo, bhi, 0);
-                    m[i].y |= r & dword_byte_mask(blo, bhi, 1);
-                    m[i].z |= r & dword_byte_mask(blo, bhi, 2);
-                    m[i].w |= r & dword_byte_mask(blo, bhi, 3);
-                }
-            }
-        }
-        __syncthreads();  // every lane done reading this round's LDS
-        return cnt;
-    };
-    auto have_f = [&]() { return f + (uint32_t)tid < n && f + (uint32_t)tid <= flast; };
-    auto load_f = [&]() { return have_f() ? *reinterpret_cast<const u32x4*>(d + f + tid) : u32x4{0, 0, 0, 0}; };
-    int cnt = pre ? round(have_f(), *pre) : round(have_f(), load_f());
-    while (cnt == Cfg::kCap) {
-        f += Cfg::kCap;
-        cnt = round(have_f(), load_f());
-    }
-    // Validation of the words of checked frames, as utf8_payload_kernel's
-    // general path: each word finds its frames in the sorted descriptors.
+    staged_masks(tile_lo, tile_hi, d, n, f0, flast, pre, s_off, s_end, s_key, tid, m);
+    // Validation of the words of checked frames: utf8_payload_kernel's general path.
     bool any = false;
     uint32_t fl = flast >= n ? n - 1 : flast;
     if (fl < f0) fl = f0;
@@ -687,26 +616,7 @@ __device__ __forceinline__ void fused_tile(uint8_t* __restrict__ base, uint64_t 
     if (__syncthreads_or(any)) {
         uint32_t prev[V];
         fused_lookback(v, edge, s_row, prev);
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint64_t a = tile_lo + 16u * (uint64_t)(tid + kBlock * i);
-            if (a >= tile_hi) continue;
-            uint32_t gl = f0, gh = fl + 1u;  // the first frame that ends after a
-            while (gl < gh) {
-                const uint32_t mid = gl + (gh - gl) / 2;
-                const kmws_desc dm = d[mid];
-                if (dm.off + dm.len <= a) gl = mid + 1; else gh = mid;
-            }
-            for (uint32_t g = gl; g <= fl; ++g) {
-                const kmws_desc dg = d[g];
-                if (dg.off >= a + 16u) break;
-                if (dg.len == 0u) continue;
-                const Utf8View gv = views[g];
-                if (!(gv.w & kUtf8Checked)) continue;
-                if (fused_word_frame_bad(v[i], prev[i], a, dg.off, dg.off + dg.len, rot_key(dg.key, dg.off), gv.w))
-                    report_bad(first_bad, gv.slot, g);
-            }
-        }
+        frames_check<true>(v, prev, tile_lo, tile_hi, d, f0, fl, views, first_bad);
     }
     // The stores come last here: the validation above loads descriptors and
     // views, and a load's wait also waits for every store issued before it.
@@ -794,8 +704,9 @@ __global__ void __launch_bounds__(kBlock) unmask_utf8_tail_kernel(uint8_t* __res
 // = wave + 4 i, the layout fused_lookback hands over.  The frame's message
 // state is not scanned for here: the host decoder walks each connection's
 // frames in order and passes the view (kmws_utf8_stream.hpp).  The unmask is the
-// pieces kernel's, byte for byte; a key of 0 stores nothing (an unmasked frame
-// of a CLIENT-mode decoder is only checked).  The look-back of the piece's
+// pieces kernel's (piece_hull, load_piece, store_piece: kmws_unmask_tile.hpp);
+// a key of 0 stores nothing (an unmasked frame of a CLIENT-mode decoder is only
+// checked).  The look-back of the piece's
 // first word is `edge`, which the HOST read before the launch: the piece before
 // belongs to another block, which may or may not have stored those bytes
 // unmasked already (the race of the fused in-place pass above; here every
@@ -817,43 +728,18 @@ __global__ void __launch_bounds__(kBlock) unmask_pieces_utf8_kernel(uint8_t* __r
     const PieceRecEdge pr = pieces[blockIdx.x];
     const kmws_desc x = d[pr.frame];
     const Utf8View fv = views[pr.frame];
-    const uint64_t end = x.off + x.len;
-    const uint64_t w0 = (x.off >> 4) + (uint64_t)pr.piece * kPieceWords;
-    const uint64_t wh = (end + 15) >> 4;
-    const uint64_t w1 = wh < w0 + kPieceWords ? wh : w0 + kPieceWords;
-    const uint32_t r = rot_key(x.key, x.off);
+    const PieceHull h = piece_hull(x, pr.piece);
     u32x4 v[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
-        v[i] = w < w1 ? *reinterpret_cast<const u32x4*>(base + 16 * w) : u32x4{0, 0, 0, 0};
-    }
-    if (x.key != 0u) {  // block-uniform
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
-            if (w >= w1) continue;
-            const uint64_t a = 16 * w;
-            if (a >= x.off && a + 16 <= end) {
-                *reinterpret_cast<u32x4*>(base + a) = v[i] ^ r;
-            } else {  // the hull's first or last word: own bytes only
-                const uint64_t lo = a > x.off ? a : x.off, hi = a + 16 < end ? a + 16 : end;
-                for (uint64_t q = lo; q < hi; ++q) {
-                    const uint32_t b = (uint32_t)(q - a);
-                    const uint32_t dw = (b & 8u) ? ((b & 4u) ? v[i].w : v[i].z) : ((b & 4u) ? v[i].y : v[i].x);
-                    base[q] = (uint8_t)((dw ^ r) >> (8 * (b & 3u)));
-                }
-            }
-        }
-    }
+    load_piece(base, h, v);
+    if (x.key != 0u) store_piece(base, x, h, v);  // block-uniform
     if (!(fv.w & kUtf8Checked)) return;  // block-uniform: binary, RSV1 and control frames end here
     uint32_t prev[V];
     fused_lookback(v, pr.piece ? pr.edge : 0u, s_row, prev);
     bool bad = false;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        const uint64_t w = w0 + threadIdx.x + (uint64_t)kBlock * i;
-        if (w < w1) bad |= fused_word_frame_bad(v[i], prev[i], 16 * w, x.off, end, r, fv.w);  // past the hull: nothing
+        const uint64_t w = h.w0 + threadIdx.x + (uint64_t)kBlock * i;
+        if (w < h.w1) bad |= fused_word_frame_bad(v[i], prev[i], 16 * w, x.off, h.end, h.r, fv.w);  // past the hull: nothing
     }
     const unsigned long long m = __ballot(bad);  // one report per wave
     if (m != 0ull && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) verdict[fv.slot] = (uint8_t)1;
@@ -872,6 +758,18 @@ static bool have_device()
 {
     static const bool have = kmws_device_count() > 0;
     return have;
+}
+
+kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
+                                   uint32_t n_streams, size_t need, size_t have)
+{
+    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
+    if (n && !ptrs_ok) return KMWS_ERR_INVALID_PARAM;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) return KMWS_ERR_INVALID_PARAM;
+    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
+    if (have < need) return KMWS_ERR_BUFFER_TOO_SMALL;
+    if (!have_device()) return KMWS_ERR_NOT_SUPPORTED;
+    return KMWS_OK;
 }
 
 // The per-frame kernels of a batch (1-3 of the list above) and the finish (5),
@@ -959,23 +857,17 @@ kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* ca
 {
     return launch_carry_copy(n_streams, carry_in, carry_out, s);
 }
-bool utf8_have_device() { return have_device(); }
 
-// The argument checks the fused entries share with kmws_utf8_validate, in its
-// order; `code`: the schedule to run.
+// The argument checks of the fused entries: the schedule to run (`code`), then
+// the stream arguments.  Every failure ahead of the workspace size is
+// KMWS_ERR_INVALID_PARAM, so the schedule's test stands in front.
 static kmws_status fused_check(const uint8_t* base, bool ptrs_ok, uint32_t n, const uint32_t* stream_first,
                                uint32_t n_streams, uint64_t span, int schedule, size_t workspace_bytes,
                                const FusedWs& w, uint32_t* code)
 {
-    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
-    if (n && !ptrs_ok) return KMWS_ERR_INVALID_PARAM;
-    if (reinterpret_cast<uintptr_t>(base) & 15u) return KMWS_ERR_INVALID_PARAM;
-    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
     *code = schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule;
     if (!valid_schedule(*code)) return KMWS_ERR_INVALID_PARAM;
-    if (n && workspace_bytes < w.total) return KMWS_ERR_BUFFER_TOO_SMALL;
-    if (!have_device()) return KMWS_ERR_NOT_SUPPORTED;
-    return KMWS_OK;
+    return utf8_stream_args_check(ptrs_ok, base, nullptr, n, stream_first, n_streams, n ? w.total : 0, workspace_bytes);
 }
 
 // Behind a launched plan (and the header parse, if any): the look-back
@@ -997,28 +889,14 @@ static kmws_status launch_fused(uint32_t code, uint8_t* base, uint64_t span, con
                            base, edges, (uint32_t)ntiles);
     launch_utf8_frames(w.u, a, base, span, descs, flags, n, 1, stream_first, n_streams, carry_in, s);
 
-    const bool temporal = temporal_stores(code);
-    constexpr uint64_t kMaxBlocks = (1ull << 32) / kBlock / 2;
     // the apply's test for the capped launches and its means (dynamic LDS the
     // kernel does not use), with this kernel's own number of blocks per CU
     const unsigned lds_pad = unmask_capped(span, n) ? lds_pad_for(kFusedBlocksPerCu, kFusedStaticLds) : 0u;
     const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
-    for (uint64_t b0 = 0; b0 < nfull; b0 += kMaxBlocks) {
-        const dim3 grid((uint32_t)(nfull - b0 < kMaxBlocks ? nfull - b0 : kMaxBlocks));
-        const uint32_t bb = (uint32_t)b0;
-        if (lds_pad && !temporal)
-            hipLaunchKernelGGL((unmask_utf8_split_kernel<true, true>), grid, dim3(kBlock), lds_pad, s, base, descs, n,
-                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
-        else if (lds_pad)
-            hipLaunchKernelGGL((unmask_utf8_split_kernel<true, false>), grid, dim3(kBlock), lds_pad, s, base, descs, n,
-                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
-        else if (!temporal)
-            hipLaunchKernelGGL((unmask_utf8_split_kernel<false, true>), grid, dim3(kBlock), 0, s, base, descs, n,
-                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
-        else
-            hipLaunchKernelGGL((unmask_utf8_split_kernel<false, false>), grid, dim3(kBlock), 0, s, base, descs, n,
-                               a.map, a.head, a.views, a.first_bad, edges, tm, bb);
-    }
+    launch_split_grid(nfull, lds_pad, temporal_stores(code), [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
+        hipLaunchKernelGGL((unmask_utf8_split_kernel<decltype(two)::value, decltype(nt)::value>), grid, dim3(kBlock), pad,
+                           s, base, descs, n, a.map, a.head, a.views, a.first_bad, edges, tm, b0);
+    });
     if (ntiles > nfull)  // the partial last tile
         hipLaunchKernelGGL(unmask_utf8_tail_kernel, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, a.map, a.head,
                            a.views, a.first_bad, edges, (uint32_t)nfull);
@@ -1042,16 +920,13 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
                                const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
                                void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
-    if (n && (!base || !descs || !flags || !out || !workspace)) return KMWS_ERR_INVALID_PARAM;
-    if (reinterpret_cast<uintptr_t>(base) & 15u) return KMWS_ERR_INVALID_PARAM;
-    if (n && (n_streams == 0u || (!stream_first && n_streams != 1u))) return KMWS_ERR_INVALID_PARAM;
     const Utf8Ws w = utf8_ws(span, n, n_streams);
-    if (n && workspace_bytes < w.total) return KMWS_ERR_BUFFER_TOO_SMALL;
-    if (!have_device()) return KMWS_ERR_NOT_SUPPORTED;
+    kmws_status st = utf8_stream_args_check(base && descs && flags && out && workspace, base, nullptr, n, stream_first,
+                                            n_streams, n ? w.total : 0, workspace_bytes);
+    if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);  // every stream's state passes through
-    kmws_status st = launch_plan(span, descs, n, workspace, w.plan_bytes, s);
+    st = launch_plan(span, descs, n, workspace, w.plan_bytes, s);
     if (st != KMWS_OK) return st;
     note_device_batch(span, s);
 
@@ -1067,16 +942,14 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
     Split sp;
     (void)split_of(KMWS_SCHED_SPLIT4, &sp);
     const TileMapping tm = tile_mapping((uint32_t)(span / kPlanTile), sp);  // the partial last tile maps to itself
-    constexpr uint64_t kMaxBlocks = (1ull << 32) / kBlock / 2;
-    for (uint64_t b0 = 0; b0 < ntiles; b0 += kMaxBlocks) {
-        const dim3 grid((uint32_t)(ntiles - b0 < kMaxBlocks ? ntiles - b0 : kMaxBlocks));
+    launch_split_grid(ntiles, 0u, false, [&](auto, auto, dim3 grid, uint32_t b0, unsigned) {
         if (masked)
             hipLaunchKernelGGL(utf8_payload_kernel<true>, grid, dim3(kBlock), 0, s, base, span, descs, n, map, head,
-                               views, first_bad, tm, (uint32_t)b0);
+                               views, first_bad, tm, b0);
         else
             hipLaunchKernelGGL(utf8_payload_kernel<false>, grid, dim3(kBlock), 0, s, base, span, descs, n, map, head,
-                               views, first_bad, tm, (uint32_t)b0);
-    }
+                               views, first_bad, tm, b0);
+    });
     launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
     return hip_status(hipGetLastError());
 }

@@ -85,6 +85,12 @@ void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_f
 // carry_out = carry_in for every stream (an empty batch).
 kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                    hipStream_t s);
-bool utf8_have_device();
+// The argument checks every UTF-8 entry makes on its streams and workspace, in
+// this order: n and n_streams below 2^31; ptrs_ok for a batch with frames; a
+// and b (either may be null) 16-byte aligned; one stream, or stream_first and at
+// least one (all KMWS_ERR_INVALID_PARAM); `have` workspace bytes against `need`
+// (KMWS_ERR_BUFFER_TOO_SMALL); a gfx950 device (KMWS_ERR_NOT_SUPPORTED).
+kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
+                                   uint32_t n_streams, size_t need, size_t have);
 
 }  // namespace kmws

@@ -928,21 +928,13 @@ def utf8_validate(base, descs, flags, out, ws: Workspace, span: Optional[int] = 
     _check_tensor(flags, "flags", 2, dev, n)
     _check_tensor(out, "out", 1, dev, n)
     _check_tensor(ws.tensor, "workspace", 1, dev)
-    ns = 1
-    if stream_first is not None:
-        _check_tensor(stream_first, "stream_first", 4, dev, 2)
-        ns = stream_first.numel() - 1
-    for name, c in (("carry_in", carry_in), ("carry_out", carry_out)):
-        if c is not None:
-            _check_tensor(c, name, 1, dev, 8 * ns)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
     span = base.numel() if span is None else span
     if span > base.numel():
         raise ValueError(f"span {span} exceeds base ({base.numel()} bytes)")
     _check(lib().kmws_utf8_validate(base.data_ptr(), span, descs.data_ptr(), flags.data_ptr(), n, int(bool(masked)),
-                                    stream_first.data_ptr() if stream_first is not None else None, ns,
-                                    carry_in.data_ptr() if carry_in is not None else None,
-                                    carry_out.data_ptr() if carry_out is not None else None,
-                                    out.data_ptr(), ws.ptr, ws.nbytes, _stream_handle(stream)),
+                                    _opt(stream_first), ns, _opt(carry_in), _opt(carry_out), out.data_ptr(), ws.ptr,
+                                    ws.nbytes, _stream_handle(stream)),
            "kmws_utf8_validate")
 
 

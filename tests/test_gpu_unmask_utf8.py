@@ -4,6 +4,7 @@ verdict reference is tests/utf8_ref.py (pinned by tests/test_utf8_ref.py); the
 expected bytes are the plain payloads the test built (Batch.plain) or the
 oracle's unmask.  Every case asserts the whole arena (gaps and rounding tail
 included), the verdicts, and status 0 (unmask_utf8_util.check_fused)."""
+import functools
 import random
 
 import numpy as np
@@ -107,11 +108,9 @@ def test_valid_wide_text_across_every_boundary(width, layout):
 
 # ---------------------------------------------------------------- 4. general path
 
-@pytest.mark.gpu
-def test_general_path_700_frames_in_one_tile():
-    """More than two LDS rounds of descriptors in one tile: text fragments with
-    code points straddling frames, PINGs, binary and RSV1 messages, empty FIN
-    frames that end inside a code point, key-0 and len-0 frames."""
+@functools.lru_cache(maxsize=None)
+def batch_700_frames():
+    """The batch, its frames and the reference's verdicts: built once for every schedule."""
     rng = random.Random(70)
     lens = [rng.choice([0, 0, 1, 2, 3, 5, 8, 13, 21, 34, 40]) for _ in range(700)]
     frames = vt.fill_messages(lens, 71) + vt.straddle_frames(rng)
@@ -122,12 +121,32 @@ def test_general_path_700_frames_in_one_tile():
         pos += len(p)
     assert len(frames) > 700 and offs[699] + len(frames[699][1]) <= 16384  # 700 frames inside the first tile
     b = Batch(frames, offs, pos + 5)
-    expect, _ = u.check_fused(b)
+    return b, frames, vt.want(b.frames)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sched", SCHEDULES)
+def test_general_path_700_frames_in_one_tile(sched):
+    """More than two LDS rounds of descriptors in one tile: text fragments with
+    code points straddling frames, PINGs, binary and RSV1 messages, empty FIN
+    frames that end inside a code point, key-0 and len-0 frames.  Under every
+    schedule, and the arena also equals what kmws_unmask_batch leaves on a fresh
+    masked copy: the plain apply's second and third rounds of the same staged
+    masks."""
+    import torch as T
+    from kuma_amd import kmws
+    b, frames, expect = batch_700_frames()
+    u.check_fused(b, expect, schedule=sched)
     assert {ref.NOT_TEXT, ref.OK, ref.BAD, ref.AFTER_BAD} <= set(expect)
     assert any(k == 0 for k in b.keys) and any(L == 0 for L in b.lens)
     empties = [i for i, (b0, p) in enumerate(frames) if b0 == (C_ | FIN) and p == b""]
     assert {int(expect[i]) for i in empties} >= {ref.OK, ref.BAD}
     assert any((b0 & 0x0F) == PING for b0, _ in frames)
+    plain = T.from_numpy(b.masked()).cuda()
+    ws = kmws.Workspace(kmws.unmask_workspace_size(b.total))
+    kmws.unmask_batch(plain, kmws.make_descs(b.offs, b.lens, b.keys.astype(np.int64)), ws, b.total)
+    assert ws.status() == 0
+    assert np.array_equal(plain.cpu().numpy(), u.expected_arena(b))
 
 
 @pytest.mark.gpu
@@ -141,9 +160,12 @@ def test_general_path_4k_fragments():
 
 # ---------------------------------------------------------------- 5. span edges
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("case", ["below_one_tile", "three_tiles_and_a_byte", "ends_on_the_last_byte"])
-def test_span_edges(case):
+SPAN_EDGE_CASES = ["below_one_tile", "three_tiles_and_a_byte", "ends_on_the_last_byte"]
+
+
+@functools.lru_cache(maxsize=None)
+def span_edge_batch(case):
+    """The batch and the reference's verdicts: built once for every schedule."""
     pool = ref.TextPool(random.Random(50), size=1 << 16)
     rng = random.Random(51)
     if case == "below_one_tile":      # 5 KiB: the tail kernel alone
@@ -162,10 +184,20 @@ def test_span_edges(case):
     if case != "below_one_tile":       # the message ends inside a code point, on the span's last byte
         frames[-1] = (T_ | FIN, frames[-1][1][:-1] + b"\xe2")
     b = Batch(frames, offs, total)
-    assert b.offs[-1] + b.lens[-1] <= total
+    return b, vt.want(b.frames)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sched", SCHEDULES)
+@pytest.mark.parametrize("case", SPAN_EDGE_CASES)
+def test_span_edges(case, sched):
+    """three_tiles_and_a_byte: the two-frame path, the split grid and the tail
+    kernel together, under every schedule."""
+    b, expect = span_edge_batch(case)
+    assert b.offs[-1] + b.lens[-1] <= b.total
     if case != "below_one_tile":
-        assert b.offs[-1] + b.lens[-1] == total
-    expect, _ = u.check_fused(b)
+        assert b.offs[-1] + b.lens[-1] == b.total
+    u.check_fused(b, expect, schedule=sched)
     assert expect[-1] == (ref.OK if case == "below_one_tile" else ref.BAD) and ref.OK in expect
 
 
