@@ -696,6 +696,76 @@ kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, cons
                                     const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- unmask and re-encode in one pass over the payload (relay) ----
+ * A relay -- a chat room, a pub/sub fan-in, a proxy, an echo -- receives masked
+ * client frames and sends the same messages on as server frames, unmasked or
+ * masked with fresh keys towards an upstream.  kmws_gather_unmask followed by
+ * kmws_encode_batch moves every payload byte four times; both keys are indexed
+ * by payload position mod 4, so unmasking with one and masking with the other
+ * is one XOR with their XOR, and these entries read the payload once and write
+ * header + payload once. */
+
+/* flags[i] of the reframe entries: emit nothing for frame i.  Honoured by
+ * kmws_reframe_batch / kmws_unpack_reframe only: kmws_encode_batch and
+ * kmws_pack_headers ignore it, as they ignore every bit above KMWS_FLAG_MASK. */
+#define KMWS_FLAG_SKIP 0x8000u
+
+/* Workspace bytes for kmws_reframe_batch / kmws_unpack_reframe: at least
+ * kmws_copy_workspace_size(n, dst_cap), plus 2 B per frame (the outgoing flags
+ * kmws_unpack_reframe derives). */
+size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap);
+
+/* descs[i] = {off, len, key}: key is the key the bytes src[off .. off+len) are
+ * masked with now (0: plain); the descriptors need no order in src and payloads
+ * may overlap, as for kmws_encode_batch.  flags[i] describes the outgoing
+ * frame: header byte 0, KMWS_FLAG_MASK if it is masked, KMWS_FLAG_SKIP.
+ * out_keys[i]: the outgoing key, used only when flags[i] & KMWS_FLAG_MASK; NULL:
+ * every outgoing key is 0.  A frame that is not skipped writes
+ * WSHandler::encodeFrameHeader of {flags[i] & 0x1FF, len, outgoing key}, then
+ * the payload bytes src[off + j] ^ keybyte(descs[i].key, j) ^ (MASK ?
+ * keybyte(outgoing key, j) : 0); frames lie back to back in dst.  A skipped
+ * frame contributes no bytes -- wire_off[i + 1] == wire_off[i] -- and its
+ * payload is never read (its off / len may point anywhere).  wire_off: n + 1
+ * entries, wire_off[n] = the total.
+ * Consequences: with every descs[i].key == 0 and no KMWS_FLAG_SKIP the output
+ * is exactly kmws_encode_batch's; with the incoming key equal to the outgoing
+ * key the payload is copied unchanged and the header carries the key.
+ * The rest is kmws_encode_batch's contract: a total above dst_cap sets status
+ * bit 1 and stores nothing; bit 4 on a look-back timeout; src and dst 16-byte
+ * aligned and not overlapping; KMWS_ERR_INVALID_PARAM for a NULL wire_off or
+ * workspace or, with frames, a NULL src / descs / flags / dst, and for a
+ * misaligned src / dst; KMWS_ERR_BUFFER_TOO_SMALL for a workspace below
+ * kmws_reframe_workspace_size(n, dst_cap); then KMWS_ERR_NOT_SUPPORTED without
+ * a gfx950 device (no CPU fallback).  Stream-ordered, no host sync, no
+ * allocation, kernel nodes only (capturable); the status word is cleared by a
+ * kernel.  n == 0: KMWS_OK, wire_off[0] = 0. */
+kmws_status kmws_reframe_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
+                               const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                               uint64_t* wire_off, void* workspace, size_t workspace_bytes, void* stream);
+
+/* kmws_unpack_headers and kmws_reframe_batch fused: the descriptor-indexed
+ * parse runs inside the scan, as in kmws_unpack_gather, and the payload pass
+ * runs once.  out_desc, out_flags (keeps the incoming mask bit), out_err and
+ * status bit 2 are exactly what kmws_unpack_gather writes.  Outgoing frame i
+ * has the parsed header byte 0 -- FIN, RSV1-3 and the opcode are kept, so a
+ * permessage-deflate message passes through -- and KMWS_FLAG_MASK iff out_mask
+ * != 0; it is skipped iff its header had an error or bit `opcode` of
+ * relay_opcodes is clear (0x0007: CONTINUE, TEXT and BINARY; 0xFFFF: everything
+ * that parsed).  dst, wire_off and the status are exactly what
+ * kmws_reframe_batch writes from those outgoing flags and out_desc on the same
+ * wire.  The outgoing flags live in the workspace.  KMWS_ERR_INVALID_PARAM for
+ * a bad mode, relay_opcodes > 0xFFFF, out_mask not 0 or 1; then the pointer and
+ * alignment rules of kmws_unpack_gather (wire_off and workspace always; wire,
+ * hdr_off, out_desc, dst with frames; wire and dst 16-byte aligned);
+ * KMWS_ERR_BUFFER_TOO_SMALL; KMWS_ERR_NOT_SUPPORTED.  out_keys may be NULL
+ * whatever out_mask is.  With status bit 2 some frames were dropped for header
+ * errors: the caller fails those connections (out_err). */
+kmws_status kmws_unpack_reframe(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys,
+                                uint8_t* dst, uint64_t dst_cap, uint64_t* wire_off,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- host-resident batches: pinned H2D -> kernel -> D2H pipeline ---- */
 typedef struct kmws_pipeline kmws_pipeline;
 

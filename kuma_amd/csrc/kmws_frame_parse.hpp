@@ -77,12 +77,13 @@ __device__ __forceinline__ uint64_t ext_len127(const u32x4& hw)
 // wire; headers within 32 bytes of its end are read byte by byte (same rules).
 // Writes out_desc[f] = {payload offset, len, key (0 if unmasked)} -- error
 // frames get len 0 and set kStatusBadHeader -- and, when given, out_flags[f]
-// (header byte 0 | mask << 8) and out_err[f] (WSError).  Returns the desc.
+// (header byte 0 | mask << 8) and out_err[f] (WSError).  Returns the desc;
+// parsed, when given, receives header byte 0 | WSError << 16.
 __device__ __forceinline__ kmws_desc unpack_one(const uint8_t* __restrict__ wire, uint64_t wire_len,
                                                 const uint64_t* __restrict__ hdr_off, uint32_t n, uint32_t f,
                                                 int mode, kmws_desc* __restrict__ out_desc,
                                                 uint16_t* __restrict__ out_flags, uint8_t* __restrict__ out_err,
-                                                WsHead* __restrict__ head)
+                                                WsHead* __restrict__ head, uint32_t* parsed = nullptr)
 {
     const uint64_t h = hdr_off[f];
     const uint64_t limit = f + 1 < n ? hdr_off[f + 1] : wire_len;  // this frame must end by the next header
@@ -172,6 +173,7 @@ __device__ __forceinline__ kmws_desc unpack_one(const uint8_t* __restrict__ wire
     out_desc[f] = o;
     if (out_flags) out_flags[f] = (uint16_t)((b0 & 0xFFu) | ((b1 >> 7) << 8));
     if (out_err) out_err[f] = err;
+    if (parsed) *parsed = (b0 & 0xFFu) | (uint32_t)err << 16;
     return o;
 }
 

@@ -25,6 +25,10 @@
 // kernels check the words of text messages, from the registers that hold them
 // after their stores, against the UTF-8 rule (kmws_utf8_dev.hpp) -- the
 // verdicts kmws_utf8_validate gives on the dense output, without reading it back.
+// Relay (kmws_reframe_batch, kmws_unpack_reframe): the same copy kernels go from
+// a masked wire to the outgoing wire in one pass -- the payload XORed once with
+// incoming key ^ outgoing key, the header carrying the outgoing key, frames
+// flagged KMWS_FLAG_SKIP (control frames, header errors) emitting nothing.
 // Header-only pack (kmws_pack_headers, kuma's iovec form): each header into a
 // 16-byte slot, with the wire offsets after reduce_kernel.  Boundary discovery on the
 // device (kmws_find_headers_streams): the serial header-chain walk, one lane
@@ -73,6 +77,50 @@ __device__ __forceinline__ void build_header(uint32_t len, uint32_t flags, uint3
     }
     h0 = lo;
     h1 = hi;
+}
+
+// ------------------------------ the reframe form ------------------------------
+// kmws_reframe_batch / kmws_unpack_reframe run the encode's copy kernels with
+// two differences, threaded through them as the policy RF (the encode, the
+// gather and the validating forms are the RF = false instantiations):
+//   two keys -- the payload lies masked with descs[f].key and leaves masked
+//     with the outgoing key, so the key the copy XORs (FrameGeom::key, the
+//     rotated keys of the unit records and chunk tables) is their XOR, and the
+//     header carries the outgoing key alone (out_key);
+//   a region may be empty -- a frame flagged KMWS_FLAG_SKIP has neither header
+//     nor payload (p0 == r0 == r1), like a zero-length payload of the gather:
+//     every size comes from region_hdr / region_pay.
+// Frame j's outgoing key: out_keys[j] if its flags say masked (a NULL array:
+// every key 0), else 0.
+template <bool RF>
+__device__ __forceinline__ uint32_t out_key(const uint32_t* __restrict__ okeys, uint32_t j, uint32_t fl)
+{
+    if constexpr (!RF) return 0u;
+    else return ((fl >> 8) & 1u) != 0u && okeys != nullptr ? okeys[j] : 0u;
+}
+// The key in a frame's header: the outgoing key, which is the copy's own key
+// in every form but the reframe.
+template <bool RF>
+__device__ __forceinline__ uint32_t hdr_key(uint32_t copy_key, uint32_t ok)
+{
+    return RF ? ok : copy_key;
+}
+// A frame's region in the output: its header bytes and its payload bytes.
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ uint32_t region_hdr(uint32_t len, uint32_t fl)
+{
+    if (RF && (fl & KMWS_FLAG_SKIP)) return 0u;
+    return HEADERS ? hdr_len(len, (fl >> 8) & 1u) : 0u;
+}
+template <bool RF>
+__device__ __forceinline__ uint32_t region_pay(uint32_t len, uint32_t fl)
+{
+    return RF && (fl & KMWS_FLAG_SKIP) ? 0u : len;
+}
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ uint64_t region_size(uint32_t len, uint32_t fl)
+{
+    return (uint64_t)region_hdr<HEADERS, RF>(len, fl) + region_pay<RF>(len, fl);
 }
 
 // ------------------------------ scan ------------------------------
@@ -156,6 +204,49 @@ struct HeaderPayloadSize {
         return SizeRaw{o.len, 0u};
     }
     __device__ V2 value(SizeRaw x) const { return V2{x.len, unit_bound(x.len)}; }
+};
+
+// The reframe's regions from the descriptors and the outgoing flags.
+struct ReframeSize {
+    static constexpr bool kHeaders = true;
+    static constexpr bool kClearsStatus = true;
+    const kmws_desc* d;
+    const uint16_t* flags;
+    __device__ SizeRaw load(uint32_t f) const { return SizeRaw{d[f].len, flags[f]}; }
+    __device__ V2 value(SizeRaw x) const
+    {
+        const uint64_t r = region_size<true, true>(x.len, x.fl);
+        return V2{r, unit_bound(r)};
+    }
+};
+// The parse fused into the reframe's scan (kmws_unpack_reframe): load() parses
+// frame f's header as HeaderPayloadSize does, derives the outgoing flags --
+// header byte 0 as parsed, the mask bit as the caller asks, KMWS_FLAG_SKIP for a
+// header error or an opcode outside relay_opcodes -- and writes them to the
+// workspace for the kernels that follow.
+struct HeaderReframeSize {
+    static constexpr bool kHeaders = true;
+    static constexpr bool kClearsStatus = false;
+    HeaderPayloadSize in;
+    uint16_t* oflags;
+    uint32_t relay_opcodes;
+    uint32_t out_mask;
+    __device__ SizeRaw load(uint32_t f) const
+    {
+        uint32_t parsed;  // header byte 0 | WSError << 16
+        const kmws_desc o = unpack_one(in.wire, in.wire_len, in.hdr_off, in.n, f, in.mode, in.out_desc, in.out_flags,
+                                       in.out_err, in.head, &parsed);
+        const uint32_t b0 = parsed & 0xFFu;
+        const bool relay = (parsed >> 16) == KMWS_WS_NOERR && ((relay_opcodes >> (b0 & 0x0Fu)) & 1u) != 0u;
+        const uint32_t fl = b0 | (out_mask ? KMWS_FLAG_MASK : 0u) | (relay ? 0u : KMWS_FLAG_SKIP);
+        oflags[f] = (uint16_t)fl;
+        return SizeRaw{o.len, fl};
+    }
+    __device__ V2 value(SizeRaw x) const
+    {
+        const uint64_t r = region_size<true, true>(x.len, x.fl);
+        return V2{r, unit_bound(r)};
+    }
 };
 
 __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x)
@@ -333,7 +424,7 @@ __device__ __forceinline__ u32x4 byte_range(int lo, int hi)
 struct FrameGeom {
     uint64_t r0, p0, r1;  // region start, payload start, region end (= payload end)
     uint64_t sdel;        // source offset - p0 (mod 2^64): source byte of output byte a = a + sdel
-    uint32_t key;         // key to apply (0 = none)
+    uint32_t key;         // key to apply (0 = none); the reframe: incoming key ^ outgoing key
     uint32_t len;
 };
 
@@ -374,17 +465,19 @@ static_assert(sizeof(UnitRec) == 32, "UnitRec is one s_load_dwordx8");
 
 // Geometry of frame j given where its region starts (regions lie back to back:
 // frame j+1 starts where frame j's payload ends).
-template <bool HEADERS>
-__device__ __forceinline__ FrameGeom geom_at(const kmws_desc& x, uint32_t fl, uint64_t r0)
+// ok: the frame's outgoing key (out_key; the reframe only).
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ FrameGeom geom_at(const kmws_desc& x, uint32_t fl, uint32_t ok, uint64_t r0)
 {
     const uint32_t mask = HEADERS ? (fl >> 8) & 1u : 1u;
+    const uint32_t len = region_pay<RF>(x.len, fl);
     FrameGeom g;
     g.r0 = r0;
-    g.p0 = r0 + (HEADERS ? hdr_len(x.len, mask) : 0u);
-    g.r1 = g.p0 + x.len;
+    g.p0 = r0 + region_hdr<HEADERS, RF>(x.len, fl);
+    g.r1 = g.p0 + len;
     g.sdel = x.off - g.p0;
-    g.key = mask ? x.key : 0u;
-    g.len = x.len;
+    g.key = RF ? x.key ^ ok : (mask ? x.key : 0u);
+    g.len = len;
     return g;
 }
 
@@ -392,15 +485,23 @@ __device__ __forceinline__ FrameGeom geom_at(const kmws_desc& x, uint32_t fl, ui
 // frame f overlaps in all but tiny-frame batches -- loaded at once (indices
 // clamped instead of branches, so the loads issue together).
 constexpr int kPre = 3;
-template <bool HEADERS>
+template <bool HEADERS, bool RF>
 __device__ __forceinline__ void load_descs(uint32_t f, uint32_t n, kmws_desc (&x)[kPre], uint32_t (&fl)[kPre],
-                                           const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags)
+                                           uint32_t (&ok)[kPre], const kmws_desc* __restrict__ d,
+                                           const uint16_t* __restrict__ flags, const uint32_t* __restrict__ okeys)
 {
 #pragma unroll
     for (int i = 0; i < kPre; ++i) {
         const uint32_t j = f + i < n ? f + i : n - 1;
         x[i] = d[j];
         fl[i] = HEADERS ? flags[j] : 0u;
+        ok[i] = 0u;
+        // every stored key, whatever the flags say, so that the loads issue together
+        if constexpr (RF) ok[i] = okeys ? okeys[j] : 0u;
+    }
+    if constexpr (RF) {
+#pragma unroll
+        for (int i = 0; i < kPre; ++i) ok[i] = (fl[i] >> 8) & 1u ? ok[i] : 0u;
     }
 }
 
@@ -408,26 +509,29 @@ __device__ __forceinline__ void load_descs(uint32_t f, uint32_t n, kmws_desc (&x
 // overlaps it -- the rare word three or more regions reach into (frames shorter
 // than a word); few registers, one frame's geometry at a time (frame j+1's
 // region starts where frame j's ends).
-template <bool HEADERS>
-__device__ __attribute__((noinline)) u32x4 compose_word_bytes(uint64_t a, uint32_t f, uint32_t n,
-                                                              const uint8_t* __restrict__ src, FrameGeom h,
-                                                              uint32_t flj, const kmws_desc* __restrict__ d,
-                                                              const uint16_t* __restrict__ flags)
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ u32x4 compose_word_bytes_impl(uint64_t a, uint32_t f, uint32_t n,
+                                                         const uint8_t* __restrict__ src, FrameGeom h, uint32_t flj,
+                                                         const kmws_desc* __restrict__ d,
+                                                         const uint16_t* __restrict__ flags,
+                                                         const uint32_t* __restrict__ okeys)
 {
     u32x4 out = u32x4{0, 0, 0, 0};
     uint32_t j = f;
+    uint32_t okj = out_key<RF>(okeys, f, flj);
     for (uint32_t b = 0; b < 16; ++b) {
         const uint64_t x = a + b;
         while (x >= h.r1 && j + 1 < n) {
             ++j;
             flj = HEADERS ? flags[j] : 0u;
-            h = geom_at<HEADERS>(d[j], flj, h.r1);
+            okj = out_key<RF>(okeys, j, flj);
+            h = geom_at<HEADERS, RF>(d[j], flj, okj, h.r1);
         }
         if (x < h.r0 || x >= h.r1) continue;  // past the last region
         uint32_t v;
         if (x < h.p0) {  // header byte x - r0
             uint64_t h0, h1;
-            build_header(h.len, flj, h.key, h0, h1);
+            build_header(h.len, flj, hdr_key<RF>(h.key, okj), h0, h1);
             const uint32_t k = (uint32_t)(x - h.r0);
             v = (uint32_t)((k < 8 ? h0 >> (8 * k) : h1 >> (8 * (k - 8))) & 0xFFu);
         } else {  // payload byte: data[i] ^ key[i % 4]
@@ -440,6 +544,30 @@ __device__ __attribute__((noinline)) u32x4 compose_word_bytes(uint64_t a, uint32
         else out.w |= v << sh;
     }
     return out;
+}
+template <bool HEADERS>
+__device__ __attribute__((noinline)) u32x4 compose_word_bytes(uint64_t a, uint32_t f, uint32_t n,
+                                                              const uint8_t* __restrict__ src, FrameGeom h,
+                                                              uint32_t flj, const kmws_desc* __restrict__ d,
+                                                              const uint16_t* __restrict__ flags)
+{
+    return compose_word_bytes_impl<HEADERS, false>(a, f, n, src, h, flj, d, flags, nullptr);
+}
+__device__ __attribute__((noinline)) u32x4 compose_word_bytes_reframe(uint64_t a, uint32_t f, uint32_t n,
+                                                                      const uint8_t* __restrict__ src, FrameGeom h,
+                                                                      uint32_t flj, const kmws_desc* __restrict__ d,
+                                                                      const uint16_t* __restrict__ flags,
+                                                                      const uint32_t* __restrict__ okeys)
+{
+    return compose_word_bytes_impl<true, true>(a, f, n, src, h, flj, d, flags, okeys);
+}
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ u32x4 compose_word(uint64_t a, uint32_t f, uint32_t n, const uint8_t* __restrict__ src,
+                                              const FrameGeom& h, uint32_t flj, const kmws_desc* __restrict__ d,
+                                              const uint16_t* __restrict__ flags, const uint32_t* __restrict__ okeys)
+{
+    if constexpr (RF) return compose_word_bytes_reframe(a, f, n, src, h, flj, d, flags, okeys);
+    else return compose_word_bytes<HEADERS>(a, f, n, src, h, flj, d, flags);
 }
 
 // Payload source words of frame h for the output word [a, a + 16): the aligned
@@ -456,15 +584,15 @@ __device__ __forceinline__ void pay_words(bool live, const FrameGeom& h, uint64_
 }
 
 // Frame h's bytes (header, then masked payload) in [a, a + 16), its payload
-// words W0/W1 from pay_words.
+// words W0/W1 from pay_words; hk: the key its header carries (hdr_key).
 template <bool HEADERS>
-__device__ __forceinline__ void put_frame(u32x4& out, uint64_t a, const FrameGeom& h, uint32_t fl, const u32x4& W0,
-                                          const u32x4& W1)
+__device__ __forceinline__ void put_frame(u32x4& out, uint64_t a, const FrameGeom& h, uint32_t fl, uint32_t hk,
+                                          const u32x4& W0, const u32x4& W1)
 {
     if (h.r0 >= a + 16) return;
     if (HEADERS && h.p0 > a && h.p0 > h.r0) {  // header bytes [r0, p0)
         uint64_t h0, h1;
-        build_header(h.len, fl, h.key, h0, h1);
+        build_header(h.len, fl, hk, h0, h1);
         const int s = (int)((int64_t)h.r0 - (int64_t)a);
         const u32x4 H = u32x4{(uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32)};
         const int he = (int)(h.p0 - h.r0) + s;
@@ -569,10 +697,11 @@ struct RowInfo {
     uint64_t F0, S0, total;
     uint32_t nf;
 };
-template <bool HEADERS>
+template <bool HEADERS, bool RF>
 __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __restrict__ src,
                                              const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                             uint32_t n, uint64_t cap, WsHead* __restrict__ head,
+                                             const uint32_t* __restrict__ okeys, uint32_t n, uint64_t cap,
+                                             WsHead* __restrict__ head,
                                              const V2* __restrict__ tiles, uint32_t ntiles,
                                              const V2* __restrict__ grp, uint64_t* __restrict__ start, RowLds& L,
                                              RowInfo& ri)
@@ -591,11 +720,11 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
     const V2 pre = tiles[rid / kRowsPerTile] + grp[rid];
     const uint64_t total = tot.a;
     kmws_desc x[kPre];
-    uint32_t fl[kPre];
-    load_descs<HEADERS>(f, n, x, fl, d, flags);
+    uint32_t fl[kPre], ok[kPre];
+    load_descs<HEADERS, RF>(f, n, x, fl, ok, d, flags, okeys);
     // this frame's region offset and first unit slot
     V2 row;
-    const uint64_t rsz = (uint64_t)(HEADERS ? hdr_len(x[0].len, (fl[0] >> 8) & 1u) : 0u) + x[0].len;
+    const uint64_t rsz = region_size<HEADERS, RF>(x[0].len, fl[0]);
     const V2 off = pre + block_excl_scan(t < nf ? V2{rsz, unit_bound(rsz)} : V2{0, 0}, s_w, row);
     const uint64_t r0 = off.a, uf = off.b, S0 = pre.b, uend = pre.b + row.b;
     if (t < nf) start[f] = r0;
@@ -608,10 +737,10 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
         return false;
     }
     FrameGeom g[kPre];
-    g[0] = geom_at<HEADERS>(x[0], fl[0], r0);
+    g[0] = geom_at<HEADERS, RF>(x[0], fl[0], ok[0], r0);
 #pragma unroll
     for (int i = 1; i < kPre; ++i) {
-        g[i] = geom_at<HEADERS>(x[i], fl[i], g[i - 1].r1);
+        g[i] = geom_at<HEADERS, RF>(x[i], fl[i], ok[i], g[i - 1].r1);
         if ((uint64_t)f + i >= n) g[i].r0 = ~0ull;  // past the last frame: overlaps nothing
     }
     if (t < nf) {
@@ -663,7 +792,7 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
                 third |= 1u;
             } else {
                 u32x4 out = u32x4{0, 0, 0, 0};
-                put_frame<HEADERS>(out, ah, F, fl[0], H0, H1);
+                put_frame<HEADERS>(out, ah, F, fl[0], hdr_key<RF>(F.key, ok[0]), H0, H1);
                 my[0] = out;
             }
         }
@@ -678,11 +807,11 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
                 continue;
             }
             u32x4 out = u32x4{0, 0, 0, 0};
-            if (i == 0) put_frame<HEADERS>(out, a, F, fl[0], T0, T1);
+            if (i == 0) put_frame<HEADERS>(out, a, F, fl[0], hdr_key<RF>(F.key, ok[0]), T0, T1);
             if (N.r0 < a + 16) {
                 if (HEADERS && N.p0 > a && N.p0 > N.r0) {  // f+1's header bytes [r0, p0)
                     uint64_t h0, h1;
-                    build_header(N.len, fl[1], N.key, h0, h1);
+                    build_header(N.len, fl[1], hdr_key<RF>(N.key, ok[1]), h0, h1);
                     const int sh = (int)((int64_t)N.r0 - (int64_t)a);
                     const u32x4 Hw = u32x4{(uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32)};
                     const int he = (int)(N.p0 - N.r0) + sh;
@@ -699,7 +828,7 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
         for (int q = 0; third != 0; ++q, third >>= 1) {
             if (third & 1u) {
                 const uint64_t a = 16u * ((uint32_t)q < head_f ? w.olo + q : w.ihi + (q - head_f));
-                my[q] = compose_word_bytes<HEADERS>(a, f, n, src, g[0], fl[0], d, flags);
+                my[q] = compose_word<HEADERS, RF>(a, f, n, src, g[0], fl[0], d, flags, okeys);
             }
         }
     }
@@ -727,19 +856,19 @@ __device__ __forceinline__ UnitRec make_rec(const FrameUnits& fu, uint32_t m, ui
     return r;
 }
 
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) prologue_kernel(const uint8_t* __restrict__ src,
-                                                          const kmws_desc* __restrict__ d,
-                                                          const uint16_t* __restrict__ flags, uint32_t n,
-                                                          uint64_t cap, WsHead* __restrict__ head,
-                                                          const V2* __restrict__ tiles, uint32_t ntiles,
-                                                          const V2* __restrict__ grp, uint64_t* __restrict__ start,
-                                                          UnitRec* __restrict__ rec, u32x4* __restrict__ edge)
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ void prologue_body(const uint8_t* src, const kmws_desc* d,
+                                              const uint16_t* flags, const uint32_t* okeys,
+                                              uint32_t n, uint64_t cap, WsHead* head,
+                                              const V2* tiles, uint32_t ntiles,
+                                              const V2* grp, uint64_t* start,
+                                              UnitRec* rec, u32x4* edge)
 {
     __shared__ RowLds L;
     RowInfo ri;
     const uint32_t t = threadIdx.x;
-    if (!row_prologue<HEADERS>(blockIdx.x, src, d, flags, n, cap, head, tiles, ntiles, grp, start, L, ri)) return;
+    if (!row_prologue<HEADERS, RF>(blockIdx.x, src, d, flags, okeys, n, cap, head, tiles, ntiles, grp, start, L, ri))
+        return;
     const uint64_t F0 = ri.F0, S0 = ri.S0;
     const uint32_t nf = ri.nf;
     const FrameUnits* s_fu = L.fu;
@@ -780,6 +909,32 @@ __global__ void __launch_bounds__(kBlock) prologue_kernel(const uint8_t* __restr
         }
         rec[S0 + sl] = r;
     }
+}
+
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) prologue_kernel(const uint8_t* __restrict__ src,
+                                                          const kmws_desc* __restrict__ d,
+                                                          const uint16_t* __restrict__ flags, uint32_t n,
+                                                          uint64_t cap, WsHead* __restrict__ head,
+                                                          const V2* __restrict__ tiles, uint32_t ntiles,
+                                                          const V2* __restrict__ grp, uint64_t* __restrict__ start,
+                                                          UnitRec* __restrict__ rec, u32x4* __restrict__ edge)
+{
+    prologue_body<HEADERS, false>(src, d, flags, nullptr, n, cap, head, tiles, ntiles, grp, start, rec, edge);
+}
+
+// The reframe's prologue; its unit records and edge words go to copy_kernel<true>.
+__global__ void __launch_bounds__(kBlock) prologue_reframe_kernel(const uint8_t* __restrict__ src,
+                                                                  const kmws_desc* __restrict__ d,
+                                                                  const uint16_t* __restrict__ flags,
+                                                                  const uint32_t* __restrict__ okeys, uint32_t n,
+                                                                  uint64_t cap, WsHead* __restrict__ head,
+                                                                  const V2* __restrict__ tiles, uint32_t ntiles,
+                                                                  const V2* __restrict__ grp,
+                                                                  uint64_t* __restrict__ start,
+                                                                  UnitRec* __restrict__ rec, u32x4* __restrict__ edge)
+{
+    prologue_body<true, true>(src, d, flags, okeys, n, cap, head, tiles, ntiles, grp, start, rec, edge);
 }
 
 __device__ __forceinline__ u32x4 shfl16(const u32x4& v, int lane)
@@ -1120,12 +1275,12 @@ __host__ __device__ __forceinline__ uint64_t chunk_count(uint64_t bytes) { retur
 // 256 frames per block, after the scan: each frame's region offset (start[f])
 // and, for every chunk whose first byte lies in the block's regions, the frame
 // holding it (cmap[c]).  Also the capacity check (status set, nothing stored).
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __restrict__ d,
-                                                           const uint16_t* __restrict__ flags, uint32_t n, uint64_t cap,
-                                                           WsHead* __restrict__ head, const V2* __restrict__ tiles,
-                                                           uint32_t ntiles, const V2* __restrict__ grp,
-                                                           uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ void chunk_map_body(const kmws_desc* d, const uint16_t* flags,
+                                               uint32_t n, uint64_t cap, WsHead* head,
+                                               const V2* tiles, uint32_t ntiles,
+                                               const V2* grp, uint64_t* start,
+                                               uint32_t* cmap)
 {
     __shared__ uint64_t s_r0[kBlock + 1];
     __shared__ V2 s_w[kBlock / 64];
@@ -1137,7 +1292,7 @@ __global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __re
     const V2 pre = tiles[blockIdx.x / kRowsPerTile] + grp[blockIdx.x];
     const kmws_desc x = d[f];
     const uint32_t fl = HEADERS ? flags[f] : 0u;
-    const uint64_t rsz = (uint64_t)(HEADERS ? hdr_len(x.len, (fl >> 8) & 1u) : 0u) + x.len;
+    const uint64_t rsz = region_size<HEADERS, RF>(x.len, fl);
     if (blockIdx.x == 0 && t == 0) head->pad[0] = 0;  // chunk_copy_kernel's dense-chunk count
     V2 row;
     const V2 off = block_excl_scan(t < nf ? V2{rsz, 0} : V2{0, 0}, s_w, row);
@@ -1164,6 +1319,27 @@ __global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __re
     }
 }
 
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __restrict__ d,
+                                                           const uint16_t* __restrict__ flags, uint32_t n, uint64_t cap,
+                                                           WsHead* __restrict__ head, const V2* __restrict__ tiles,
+                                                           uint32_t ntiles, const V2* __restrict__ grp,
+                                                           uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
+{
+    chunk_map_body<HEADERS, false>(d, flags, n, cap, head, tiles, ntiles, grp, start, cmap);
+}
+
+__global__ void __launch_bounds__(kBlock) chunk_map_reframe_kernel(const kmws_desc* __restrict__ d,
+                                                                   const uint16_t* __restrict__ flags, uint32_t n,
+                                                                   uint64_t cap, WsHead* __restrict__ head,
+                                                                   const V2* __restrict__ tiles, uint32_t ntiles,
+                                                                   const V2* __restrict__ grp,
+                                                                   uint64_t* __restrict__ start,
+                                                                   uint32_t* __restrict__ cmap)
+{
+    chunk_map_body<true, true>(d, flags, n, cap, head, tiles, ntiles, grp, start, cmap);
+}
+
 // One frame of a chunk's table (LDS), 48 B: its geometry relative to the
 // chunk's first byte A0 (clamped to +-2^30: only offsets within a few bytes of
 // the chunk matter), its source pointer per output offset, the rotated key of
@@ -1171,7 +1347,7 @@ __global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __re
 // header bytes.
 struct ChunkFrame {
     int32_t r0, p0, r1;  // region start, payload start, region end - A0
-    uint32_t rk;         // rot_key(key, p0) (0: no mask)
+    uint32_t rk;         // rot_key(key, p0) (0: no mask); the reframe: of incoming key ^ outgoing key
     uint64_t sbase;      // source byte of output offset o = sbase + o
     uint8_t h[16];       // the header's bytes (encode)
     uint64_t pad;        // the validating gather: the frame's Utf8View (slot, then w)
@@ -1225,10 +1401,11 @@ __device__ __forceinline__ u32x4 copy_src_load(const uint8_t* p)
 // chunk's first word comes from the source (lookback_issue).  A chunk with more
 // than 64 boundary words (whose surplus is stored from LDS, not from the
 // registers validated here) goes to chunk_dense_kernel as well.
-template <bool HEADERS, bool UTF8, class U>
+template <bool HEADERS, bool UTF8, bool RF, class U>
 __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                            const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                           uint32_t n, const uint64_t* __restrict__ start,
+                                           const uint32_t* __restrict__ okeys, uint32_t n,
+                                           const uint64_t* __restrict__ start,
                                            const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
                                            WsHead* __restrict__ head, uint32_t* __restrict__ dense,
                                            uint64_t chunk_base, uint32_t split, const U& u)
@@ -1264,16 +1441,17 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
         const kmws_desc x = d[j];
         const uint32_t fl = HEADERS ? flags[j] : 0u;
         const uint32_t mask = HEADERS ? (fl >> 8) & 1u : 1u;
-        const uint64_t r0 = start[j], p0 = r0 + (HEADERS ? hdr_len(x.len, mask) : 0u);
-        const uint32_t key = mask ? x.key : 0u;
+        const uint32_t ok = out_key<RF>(okeys, j, fl);
+        const uint64_t r0 = start[j], p0 = r0 + region_hdr<HEADERS, RF>(x.len, fl);
+        const uint32_t key = RF ? x.key ^ ok : (mask ? x.key : 0u);
         ChunkFrame e;
         e.r0 = rel32(r0, A0);
         e.p0 = rel32(p0, A0);
-        e.r1 = rel32(p0 + x.len, A0);
+        e.r1 = rel32(p0 + region_pay<RF>(x.len, fl), A0);
         e.rk = key ? rot_key(key, p0) : 0u;
         e.sbase = (uint64_t)(uintptr_t)src + x.off - (p0 - A0);
         uint64_t h0 = 0, h1 = 0;
-        if (HEADERS) build_header(x.len, fl, key, h0, h1);
+        if (HEADERS) build_header(x.len, fl, hdr_key<RF>(key, ok), h0, h1);
         __builtin_memcpy(e.h, &h0, 8);
         __builtin_memcpy(e.h + 8, &h1, 8);
         if constexpr (UTF8) {
@@ -1492,7 +1670,25 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
                                                             uint32_t* __restrict__ dense, uint64_t chunk_base,
                                                             uint32_t split)
 {
-    chunk_body<HEADERS, false>(src, dst, d, flags, n, start, cmap, tot, head, dense, chunk_base, split, NoUtf8{});
+    chunk_body<HEADERS, false, false>(src, dst, d, flags, nullptr, n, start, cmap, tot, head, dense, chunk_base, split,
+                                      NoUtf8{});
+}
+
+// Registers: see DESIGN 4 ("the reframe").
+__global__ void __launch_bounds__(kBlock) chunk_copy_reframe_kernel(const uint8_t* __restrict__ src,
+                                                                    uint8_t* __restrict__ dst,
+                                                                    const kmws_desc* __restrict__ d,
+                                                                    const uint16_t* __restrict__ flags,
+                                                                    const uint32_t* __restrict__ okeys, uint32_t n,
+                                                                    const uint64_t* __restrict__ start,
+                                                                    const uint32_t* __restrict__ cmap,
+                                                                    const V2* __restrict__ tot,
+                                                                    WsHead* __restrict__ head,
+                                                                    uint32_t* __restrict__ dense, uint64_t chunk_base,
+                                                                    uint32_t split)
+{
+    chunk_body<true, false, true>(src, dst, d, flags, okeys, n, start, cmap, tot, head, dense, chunk_base, split,
+                                  NoUtf8{});
 }
 
 // Registers: see DESIGN 4 ("the validating gather").
@@ -1505,7 +1701,7 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_utf8_kernel(const uint8_t* 
                                                                  uint32_t* __restrict__ dense, uint64_t chunk_base,
                                                                  uint32_t split, Utf8Gather u)
 {
-    chunk_body<false, true>(src, dst, d, nullptr, n, start, cmap, tot, head, dense, chunk_base, split, u);
+    chunk_body<false, true, false>(src, dst, d, nullptr, nullptr, n, start, cmap, tot, head, dense, chunk_base, split, u);
 }
 
 // The chunks chunk_copy_kernel listed (more than kChunkFrames frames: regions
@@ -1514,10 +1710,11 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_utf8_kernel(const uint8_t* 
 // not matter; a batch of small frames takes the unit form instead (below).
 // UTF8 (the validating gather): every word is also checked against the frames
 // in it (check_word_frames).
-template <bool HEADERS, bool UTF8, class U>
+template <bool HEADERS, bool UTF8, bool RF, class U>
 __device__ __forceinline__ void dense_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                            const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                           uint32_t n, const uint64_t* __restrict__ start,
+                                           const uint32_t* __restrict__ okeys, uint32_t n,
+                                           const uint64_t* __restrict__ start,
                                            const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
                                            const WsHead* __restrict__ head, const uint32_t* __restrict__ dense,
                                            const U& u)
@@ -1539,8 +1736,8 @@ __device__ __forceinline__ void dense_body(const uint8_t* __restrict__ src, uint
                 if (start[mid] <= a) lo = mid; else hi = mid;
             }
             const uint32_t fl = HEADERS ? flags[lo] : 0u;
-            const FrameGeom g = geom_at<HEADERS>(d[lo], fl, start[lo]);
-            const u32x4 v = compose_word_bytes<HEADERS>(a, lo, n, src, g, fl, d, flags);
+            const FrameGeom g = geom_at<HEADERS, RF>(d[lo], fl, out_key<RF>(okeys, lo, fl), start[lo]);
+            const u32x4 v = compose_word<HEADERS, RF>(a, lo, n, src, g, fl, d, flags, okeys);
             if (a + 16 <= total) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst + a));
             else store_word_bytes(dst, a, total, v);
             if constexpr (UTF8) check_word_frames(v, a, lo, src, u);
@@ -1558,7 +1755,21 @@ __global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __re
                                                              const WsHead* __restrict__ head,
                                                              const uint32_t* __restrict__ dense)
 {
-    dense_body<HEADERS, false>(src, dst, d, flags, n, start, cmap, tot, head, dense, NoUtf8{});
+    dense_body<HEADERS, false, false>(src, dst, d, flags, nullptr, n, start, cmap, tot, head, dense, NoUtf8{});
+}
+
+__global__ void __launch_bounds__(kBlock) chunk_dense_reframe_kernel(const uint8_t* __restrict__ src,
+                                                                     uint8_t* __restrict__ dst,
+                                                                     const kmws_desc* __restrict__ d,
+                                                                     const uint16_t* __restrict__ flags,
+                                                                     const uint32_t* __restrict__ okeys, uint32_t n,
+                                                                     const uint64_t* __restrict__ start,
+                                                                     const uint32_t* __restrict__ cmap,
+                                                                     const V2* __restrict__ tot,
+                                                                     const WsHead* __restrict__ head,
+                                                                     const uint32_t* __restrict__ dense)
+{
+    dense_body<true, false, true>(src, dst, d, flags, okeys, n, start, cmap, tot, head, dense, NoUtf8{});
 }
 
 __global__ void __launch_bounds__(kBlock) chunk_dense_utf8_kernel(const uint8_t* __restrict__ src,
@@ -1570,7 +1781,7 @@ __global__ void __launch_bounds__(kBlock) chunk_dense_utf8_kernel(const uint8_t*
                                                                   const WsHead* __restrict__ head,
                                                                   const uint32_t* __restrict__ dense, Utf8Gather u)
 {
-    dense_body<false, true>(src, dst, d, nullptr, n, start, cmap, tot, head, dense, u);
+    dense_body<false, true, false>(src, dst, d, nullptr, nullptr, n, start, cmap, tot, head, dense, u);
 }
 
 // ------------------------------ header unpack / validate ------------------------------
@@ -1826,12 +2037,11 @@ __global__ void __launch_bounds__(kBlock) zero_words_kernel(uint64_t* __restrict
 // dense count are zeroed by the launch before it.  The last tile writes the
 // total (start[n] and tot) and the capacity check; every tile clips its chunk
 // map to the capacity, so an oversized batch writes nothing out of bounds.
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __restrict__ d,
-                                                            const uint16_t* __restrict__ flags, uint32_t n,
-                                                            uint64_t cap, WsHead* __restrict__ head,
-                                                            uint64_t* __restrict__ st, V2* __restrict__ tot,
-                                                            uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
+template <bool HEADERS, bool RF>
+__device__ __forceinline__ void chunk_scan_body(const kmws_desc* d, const uint16_t* flags,
+                                                uint32_t n, uint64_t cap, WsHead* head,
+                                                uint64_t* st, V2* tot,
+                                                uint64_t* start, uint32_t* cmap)
 {
     __shared__ uint64_t s_sz[kScanTile];  // region sizes, then offsets
     __shared__ uint64_t s_w[kBlock / 64];
@@ -1852,7 +2062,7 @@ __global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __r
 #pragma unroll
     for (int i = 0; i < kScanItems; ++i) {
         const uint64_t f = F + (uint64_t)i * kBlock + t;
-        const uint64_t r = (uint64_t)(HEADERS ? hdr_len(len[i], (fl[i] >> 8) & 1u) : 0u) + len[i];
+        const uint64_t r = region_size<HEADERS, RF>(len[i], fl[i]);
         part += f < n ? r : 0;
         s_sz[i * kBlock + t] = f < n ? r : 0;
     }
@@ -1917,6 +2127,26 @@ __global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __r
         }
         cmap[c] = (uint32_t)(F + lo);
     }
+}
+
+template <bool HEADERS>
+__global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __restrict__ d,
+                                                            const uint16_t* __restrict__ flags, uint32_t n,
+                                                            uint64_t cap, WsHead* __restrict__ head,
+                                                            uint64_t* __restrict__ st, V2* __restrict__ tot,
+                                                            uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
+{
+    chunk_scan_body<HEADERS, false>(d, flags, n, cap, head, st, tot, start, cmap);
+}
+
+__global__ void __launch_bounds__(kBlock) chunk_scan_reframe_kernel(const kmws_desc* __restrict__ d,
+                                                                    const uint16_t* __restrict__ flags, uint32_t n,
+                                                                    uint64_t cap, WsHead* __restrict__ head,
+                                                                    uint64_t* __restrict__ st, V2* __restrict__ tot,
+                                                                    uint64_t* __restrict__ start,
+                                                                    uint32_t* __restrict__ cmap)
+{
+    chunk_scan_body<true, true>(d, flags, n, cap, head, st, tot, start, cmap);
 }
 
 // ------------------------------ header-chain walk, many streams ------------------------------
@@ -2118,10 +2348,11 @@ static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, CopyWs& c
 // (usually none: the grid of chunk_dense_kernel exits at once).  ul: the
 // validating gather (never with HEADERS), whose per-frame kernels run around
 // the copy grid.
-template <bool HEADERS>
+// okeys: the reframe's outgoing keys (RF; may be NULL).
+template <bool HEADERS, bool RF>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                      const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s, const Utf8Launch* ul)
+                                     hipStream_t s, const Utf8Launch* ul, const uint32_t* okeys)
 {
     const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
     constexpr uint64_t kWaves = kBlock / 64;
@@ -2134,6 +2365,9 @@ static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t 
         if (ul)
             hipLaunchKernelGGL(chunk_copy_utf8_kernel, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
                                c.tiles + nt, c.head, c.dense, c0, kChunkSplit, u);
+        else if constexpr (RF)
+            hipLaunchKernelGGL(chunk_copy_reframe_kernel, grid, dim3(kBlock), 0, s, src, dst, d, flags, okeys, n, start,
+                               c.cmap, c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
         else
             hipLaunchKernelGGL(chunk_copy_kernel<HEADERS>, grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
                                c.cmap, c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
@@ -2142,6 +2376,9 @@ static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t 
         hipLaunchKernelGGL(chunk_dense_utf8_kernel, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
                            c.tiles + nt, c.head, c.dense, u);
         launch_utf8_after_copy(*ul, n, s);
+    } else if constexpr (RF) {
+        hipLaunchKernelGGL(chunk_dense_reframe_kernel, dense_grid, dim3(kBlock), 0, s, src, dst, d, flags, okeys, n,
+                           start, c.cmap, c.tiles + nt, c.head, c.dense);
     } else {
         hipLaunchKernelGGL(chunk_dense_kernel<HEADERS>, dense_grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
                            c.cmap, c.tiles + nt, c.head, c.dense);
@@ -2151,14 +2388,18 @@ static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t 
 
 // The chunk form behind reduce + scan (the fused unpack-gather, whose scan
 // parses the headers): chunk_map, then the copy.
-template <bool HEADERS>
+template <bool HEADERS, bool RF>
 static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
                                  const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
-                                 const Utf8Launch* ul)
+                                 const Utf8Launch* ul, const uint32_t* okeys)
 {
-    hipLaunchKernelGGL(chunk_map_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
-                       c.head, c.tiles, nt, c.grp, start, c.cmap);
-    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
+    if constexpr (RF)
+        hipLaunchKernelGGL(chunk_map_reframe_kernel, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
+                           c.head, c.tiles, nt, c.grp, start, c.cmap);
+    else
+        hipLaunchKernelGGL(chunk_map_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
+                           c.head, c.tiles, nt, c.grp, start, c.cmap);
+    return launch_chunk_copy<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
 }
 
 // The chunk form's front in one pass: one look-back pass (chunk_scan_kernel)
@@ -2167,10 +2408,10 @@ static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap,
 // (profiles/r04aq_chunk_one_pass_ab.txt): cfg4 0.752-0.767 / 0.774-0.779
 // against 0.749-0.766 / 0.772-0.777, 1-300 B frames 0.35-0.40 / 0.45-0.49
 // against 0.34-0.39 / 0.44-0.48 (encode / gather).
-template <bool HEADERS>
+template <bool HEADERS, bool RF>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                           const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
-                                          hipStream_t s, const Utf8Launch* ul)
+                                          hipStream_t s, const Utf8Launch* ul, const uint32_t* okeys)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
     // head | tile totals (nt + 1) | the row-prefix area, whose first nt words hold the states
@@ -2178,22 +2419,30 @@ static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint
     const uint64_t zb = (words + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(zero_words_kernel, dim3((uint32_t)(zb < 1024 ? zb : 1024)), dim3(kBlock), 0, s,
                        reinterpret_cast<uint64_t*>(c.head), words);
-    hipLaunchKernelGGL(chunk_scan_kernel<HEADERS>, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
-                       reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
-    return launch_chunk_copy<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
+    if constexpr (RF)
+        hipLaunchKernelGGL(chunk_scan_reframe_kernel, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
+                           reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
+    else
+        hipLaunchKernelGGL(chunk_scan_kernel<HEADERS>, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
+                           reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
+    return launch_chunk_copy<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
 }
 
 // The copy form after the scan: chunks (small mean) or the prologue and the
 // unit copy grid.
-template <bool HEADERS>
+template <bool HEADERS, bool RF = false>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
                                     const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                                    const Utf8Launch* ul = nullptr)
+                                    const Utf8Launch* ul = nullptr, const uint32_t* okeys = nullptr)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
-    if (use_chunks(n, cap)) return launch_chunks<HEADERS>(src, dst, cap, start, d, flags, n, c, nt, s, ul);
-    hipLaunchKernelGGL(prologue_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, n, cap,
-                       c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
+    if (use_chunks(n, cap)) return launch_chunks<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
+    if constexpr (RF)
+        hipLaunchKernelGGL(prologue_reframe_kernel, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, okeys,
+                           n, cap, c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
+    else
+        hipLaunchKernelGGL(prologue_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, n,
+                           cap, c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
     // Occupancy: runs of large frames stream faster with 5 blocks per CU (fewer
     // concurrent DRAM streams; capped by 32 KiB of dynamic LDS per block),
     // batches of small frames need every wave slot to hide their per-unit
@@ -2220,20 +2469,22 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
 // Encode / gather: reduce (row and tile totals), scan the tile totals, the
 // prologue (offsets, edge words, unit records), the copy grid.  Four launches,
 // stream-ordered, nothing on the host in between.
-template <bool HEADERS>
+template <bool HEADERS, bool RF = false>
 static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
                                const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                               const Utf8Launch* ul = nullptr)
+                               const Utf8Launch* ul = nullptr, const uint32_t* okeys = nullptr)
 {
     if (n == 0) {
         if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
         return launch_zero(start, sizeof(uint64_t), s);
     }
-    if (use_chunks(n, cap)) return launch_chunks_one_pass<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
-    const kmws_status st = HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
-                                   : launch_reduce(PayloadSize{d}, n, start, c, s);
+    if (use_chunks(n, cap))
+        return launch_chunks_one_pass<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, s, ul, okeys);
+    const kmws_status st = RF        ? launch_reduce(ReframeSize{d, flags}, n, start, c, s)
+                           : HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
+                                     : launch_reduce(PayloadSize{d}, n, start, c, s);
     if (st != KMWS_OK) return st;
-    return launch_copy_tail<HEADERS>(src, dst, cap, start, d, flags, n, c, s, ul);
+    return launch_copy_tail<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, s, ul, okeys);
 }
 
 }  // namespace kmws
@@ -2295,6 +2546,72 @@ kmws_status kmws_unpack_gather(const uint8_t* wire, uint64_t wire_len, const uin
                                    n, dst_off, c, s);
     if (st != KMWS_OK) return st;
     return launch_copy_tail<false>(wire, dst, dst_cap, dst_off, out_desc, nullptr, n, c, s);
+}
+
+// ---- unmask and re-encode in one pass over the payload ----
+// The copy's workspace, then the outgoing flags kmws_unpack_reframe derives (2 B per frame).
+size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap)
+{
+    return r256(copy_ws_size(n, dst_cap)) + r16(2ull * n);
+}
+
+static bool have_device()
+{
+    static const bool have = kmws_device_count() > 0;
+    return have;
+}
+
+// kmws_encode_batch's checks and return values on the reframe's workspace size.
+static kmws_status reframe_check(bool ptrs_ok, const void* src, const void* dst, uint32_t n, uint64_t dst_cap,
+                                 void* workspace, size_t workspace_bytes, CopyWs& c)
+{
+    const size_t need = kmws_reframe_workspace_size(n, dst_cap);
+    if (!ptrs_ok || (reinterpret_cast<uintptr_t>(dst) & 15u) || (reinterpret_cast<uintptr_t>(src) & 15u) ||
+        !workspace || workspace_bytes < need || !carve(workspace, workspace_bytes, n, dst_cap, c))
+        return workspace && workspace_bytes < need ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_ERR_INVALID_PARAM;
+    return have_device() ? KMWS_OK : KMWS_ERR_NOT_SUPPORTED;
+}
+
+kmws_status kmws_reframe_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
+                               const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                               uint64_t* wire_off, void* workspace, size_t workspace_bytes, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    CopyWs c;
+    const kmws_status st = reframe_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
+                                         workspace, workspace_bytes, c);
+    if (st != KMWS_OK) return st;
+    if (n) kmws::note_device_batch(2 * dst_cap, s);
+    return launch_copy<true, true>(src, dst, dst_cap, wire_off, descs, flags, n, c, s, nullptr, out_keys);
+}
+
+// The parse fused into the reframe's scan: status cleared, reduce over the
+// outgoing regions (writing the descriptors and, to the workspace, the outgoing
+// flags), scan, then the chunk map or the prologue, and the copy.
+kmws_status kmws_unpack_reframe(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys, uint8_t* dst,
+                                uint64_t dst_cap, uint64_t* wire_off, void* workspace, size_t workspace_bytes,
+                                void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    CopyWs c;
+    if ((mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) || relay_opcodes > 0xFFFFu ||
+        (out_mask != 0 && out_mask != 1))
+        return KMWS_ERR_INVALID_PARAM;
+    const kmws_status ck = reframe_check(wire_off && (!n || (wire && hdr_off && out_desc && dst)), wire, dst, n,
+                                         dst_cap, workspace, workspace_bytes, c);
+    if (ck != KMWS_OK) return ck;
+    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    if (n == 0) return launch_zero(wire_off, sizeof(uint64_t), s);
+    kmws::note_device_batch(wire_len + dst_cap, s);
+    uint16_t* oflags = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)));
+    const HeaderReframeSize size{HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
+                                                   c.head},
+                                 oflags, relay_opcodes, (uint32_t)out_mask};
+    const kmws_status st = launch_reduce(size, n, wire_off, c, s);
+    if (st != KMWS_OK) return st;
+    return launch_copy_tail<true, true>(wire, dst, dst_cap, wire_off, out_desc, oflags, n, c, s, nullptr, out_keys);
 }
 
 // ---- gather, unmask and UTF-8 check in one pass over the payload ----

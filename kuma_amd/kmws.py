@@ -25,6 +25,7 @@ WS_NOERR, WS_NEED_MORE_DATA, WS_INVALID_FRAME, WS_INVALID_LENGTH = 0, 1, 5, 6
 WS_PROTOCOL_ERROR, WS_CLOSED, WS_DESTROYED = 7, 8, 9
 MAX_HEADER_SIZE = 14
 FLAG_MASK = 0x100
+FLAG_SKIP = 0x8000  # KMWS_FLAG_SKIP: reframe_batch / unpack_reframe emit nothing for the frame
 DEVICE_AUTO = -1  # KMWS_DEVICE_AUTO: the calling thread's device
 DEVICE_POLICY_NUMA, DEVICE_POLICY_ROUND_ROBIN, DEVICE_POLICY_FIRST = 0, 1, 2
 
@@ -50,6 +51,7 @@ EXPORTS = [
     "kmws_utf8_workspace_size", "kmws_utf8_validate",
     "kmws_unmask_utf8_workspace_size", "kmws_unmask_utf8_batch", "kmws_unpack_unmask_utf8",
     "kmws_gather_utf8_workspace_size", "kmws_gather_unmask_utf8", "kmws_unpack_gather_utf8",
+    "kmws_reframe_workspace_size", "kmws_reframe_batch", "kmws_unpack_reframe",
 ]
 # per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
 UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
@@ -207,6 +209,9 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_gather_unmask_utf8": (i32, [u8p, vp, vp, u32, u8p, u64, vp, vp, u32, vp, vp, u8p, vp, sz, vp]),
         "kmws_unpack_gather_utf8": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, u8p, u64, vp, vp, u32, vp, vp, u8p, vp,
                                           sz, vp]),
+        "kmws_reframe_workspace_size": (sz, [u32, u64]),
+        "kmws_reframe_batch": (i32, [u8p, vp, vp, vp, u32, u8p, u64, vp, vp, sz, vp]),
+        "kmws_unpack_reframe": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, u32, i32, vp, u8p, u64, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1049,6 +1054,66 @@ def unpack_gather(wire, hdr_off, mode: int, out_desc, out_flags, out_err, dst, d
     _check(lib().kmws_unpack_gather(wire.data_ptr(), wire_len, hdr_off.data_ptr(), n, mode, out_desc.data_ptr(),
                                     _opt(out_flags), _opt(out_err), dst.data_ptr(), dst.numel(), dst_off.data_ptr(),
                                     ws.ptr, ws.nbytes, _stream_handle(stream)), "kmws_unpack_gather")
+
+
+def reframe_workspace_size(n: int, dst_cap: int) -> int:
+    return lib().kmws_reframe_workspace_size(n, dst_cap)
+
+
+def reframe_batch(src, descs, flags, out_keys, dst, wire_off, ws: Workspace, stream=None,
+                  check: bool = False) -> None:
+    """kmws_reframe_batch: unmask with descs' keys and re-encode with flags / out_keys
+    in one pass.  descs (n,2) int64, flags int16 (n,) (header byte 0 | FLAG_MASK |
+    FLAG_SKIP), out_keys int32 (n,) or None (every outgoing key 0), wire_off int64
+    (n+1,); dst.numel() is dst_cap; ws: reframe_workspace_size(n, dst.numel()).
+    Stream-ordered; check=True synchronizes and raises on a nonzero workspace
+    status (wire_off and dst are valid only when it is 0)."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(src, "src", 1, dev)
+    _check_tensor(flags, "flags", 2, dev, n)
+    if out_keys is not None:
+        _check_tensor(out_keys, "out_keys", 4, dev, n)
+    _check_tensor(dst, "dst", 1, dev)
+    _check_tensor(wire_off, "wire_off", 8, dev, n + 1)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    _check(lib().kmws_reframe_batch(src.data_ptr(), descs.data_ptr(), flags.data_ptr(), _opt(out_keys), n,
+                                    dst.data_ptr(), dst.numel(), wire_off.data_ptr(), ws.ptr, ws.nbytes,
+                                    _stream_handle(stream)), "kmws_reframe_batch")
+    if check and n:
+        _raise_on_status(ws, stream, "kmws_reframe_batch", "wire_off")
+
+
+def unpack_reframe(wire, hdr_off, mode: int, out_desc, out_flags, out_err, relay_opcodes: int, out_mask: bool,
+                   out_keys, dst, wire_off, ws: Workspace, wire_len: Optional[int] = None, stream=None,
+                   check: bool = False) -> None:
+    """kmws_unpack_reframe: the header parse inside the reframe's scan, then the
+    frames whose opcode bit is set in relay_opcodes re-encoded into dst (masked
+    with out_keys iff out_mask); ws: reframe_workspace_size(n, dst.numel()).
+    check=True synchronizes and raises on a nonzero workspace status -- bit 2
+    (frames dropped for header errors, see out_err) included."""
+    wire_len = wire.numel() if wire_len is None else wire_len
+    n = hdr_off.shape[0]
+    dev = wire.device
+    _check_tensor(hdr_off, "hdr_off", 8, dev, n)
+    _check_tensor(out_desc, "out_desc", 8, dev, 2 * n)
+    if out_flags is not None:
+        _check_tensor(out_flags, "out_flags", 2, dev, n)
+    if out_err is not None:
+        _check_tensor(out_err, "out_err", 1, dev, n)
+    if out_keys is not None:
+        _check_tensor(out_keys, "out_keys", 4, dev, n)
+    _check_tensor(dst, "dst", 1, dev)
+    _check_tensor(wire_off, "wire_off", 8, dev, n + 1)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    if wire.numel() < wire_len:
+        raise ValueError("wire shorter than wire_len")
+    _check(lib().kmws_unpack_reframe(wire.data_ptr(), wire_len, hdr_off.data_ptr(), n, mode, out_desc.data_ptr(),
+                                     _opt(out_flags), _opt(out_err), int(relay_opcodes), int(bool(out_mask)),
+                                     _opt(out_keys), dst.data_ptr(), dst.numel(), wire_off.data_ptr(), ws.ptr,
+                                     ws.nbytes, _stream_handle(stream)), "kmws_unpack_reframe")
+    if check and n:
+        _raise_on_status(ws, stream, "kmws_unpack_reframe", "wire_off")
 
 
 def gather_utf8_workspace_size(n: int, dst_cap: int, n_streams: int = 1) -> int:
