@@ -33,6 +33,16 @@
 // 16-byte slot, with the wire offsets after reduce_kernel.  Boundary discovery on the
 // device (kmws_find_headers_streams): the serial header-chain walk, one lane
 // per stream.
+//
+// A variant of the copy is a form ("forms" below): encode, gather, reframe and
+// the validating gather are four small structs, and every stage -- prologue,
+// unit copy, chunk map, chunk scan, chunk copy, dense chunks -- is one kernel
+// template taking the form by value as its last argument, launched from one
+// place.  To add a variant, write its form struct (the three facts, the device
+// arguments only it reads), extend form_exists and whichever of flags_of /
+// out_key / copy_key / region_* it answers differently, and add its exported
+// entry: copy_args_check, then launch_copy (or, behind a scan of its own,
+// launch_reduce and launch_copy_tail) with the form.
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
 #include "kmws_utf8_dev.hpp"
@@ -79,10 +89,24 @@ __device__ __forceinline__ void build_header(uint32_t len, uint32_t flags, uint3
     h1 = hi;
 }
 
-// ------------------------------ the reframe form ------------------------------
+// ------------------------------ forms ------------------------------
+// A variant of the copy is a form: a small struct, passed by value as the last
+// argument of every stage kernel, that says at compile time what its output
+// regions are and carries the device arguments only it reads.
+//   kHeaders: a region is the frame's header, then its payload (else: payload only);
+//   kReframe: two keys and empty regions (below);
+//   kUtf8:    the words of text messages are checked after their stores.
+// Four exist.  Everything a kernel asks of a form goes through the helpers
+// after them (flags_of, out_key, stored_key, hdr_key, copy_key, region_*).
+struct EncodeForm {  // kmws_encode_batch
+    static constexpr bool kHeaders = true, kReframe = false, kUtf8 = false;
+    const uint16_t* flags;
+};
+struct GatherForm {  // kmws_gather_unmask, kmws_unpack_gather: every frame masked, no flags read
+    static constexpr bool kHeaders = false, kReframe = false, kUtf8 = false;
+};
 // kmws_reframe_batch / kmws_unpack_reframe run the encode's copy kernels with
-// two differences, threaded through them as the policy RF (the encode, the
-// gather and the validating forms are the RF = false instantiations):
+// two differences:
 //   two keys -- the payload lies masked with descs[f].key and leaves masked
 //     with the outgoing key, so the key the copy XORs (FrameGeom::key, the
 //     rotated keys of the unit records and chunk tables) is their XOR, and the
@@ -90,37 +114,100 @@ __device__ __forceinline__ void build_header(uint32_t len, uint32_t flags, uint3
 //   a region may be empty -- a frame flagged KMWS_FLAG_SKIP has neither header
 //     nor payload (p0 == r0 == r1), like a zero-length payload of the gather:
 //     every size comes from region_hdr / region_pay.
-// Frame j's outgoing key: out_keys[j] if its flags say masked (a NULL array:
-// every key 0), else 0.
-template <bool RF>
-__device__ __forceinline__ uint32_t out_key(const uint32_t* __restrict__ okeys, uint32_t j, uint32_t fl)
+// Registers of its chunk copy: see DESIGN 4 ("the reframe").
+struct ReframeForm {
+    static constexpr bool kHeaders = true, kReframe = true, kUtf8 = false;
+    const uint16_t* flags;
+    const uint32_t* okeys;  // the outgoing keys; NULL: every key 0
+};
+// The validating gather (kmws_gather_unmask_utf8, kmws_unpack_gather_utf8):
+// what its copy kernels read besides the copy's own arguments -- each frame's
+// view and the verdict words (kmws_utf8_dev.hpp), and the frames in output
+// space: frame g is [start[g], start[g] + d[g].len).  Built on the host by
+// launch_utf8_before_copy; the stages before the copy grid run as GatherForm.
+// Registers ("the validating gather"): the unit copy 98 VGPRs, 4
+// waves per SIMD, no scratch -- asking the allocator for the 5 waves per SIMD
+// that the large-frame launches' dynamic LDS allows costs 12 B of scratch per
+// lane; the chunk copy 94 VGPRs, 5 waves per SIMD.
+struct Utf8GatherForm {
+    static constexpr bool kHeaders = false, kReframe = false, kUtf8 = true;
+    const Utf8View* views;
+    uint32_t* first_bad;
+    const kmws_desc* d;
+    const uint64_t* start;
+    uint32_t n;
+};
+template <class Form>
+constexpr bool form_exists()
 {
-    if constexpr (!RF) return 0u;
-    else return ((fl >> 8) & 1u) != 0u && okeys != nullptr ? okeys[j] : 0u;
+    return (!Form::kReframe || Form::kHeaders) && (!Form::kUtf8 || (!Form::kHeaders && !Form::kReframe)) &&
+           std::is_trivially_copyable_v<Form>;
+}
+// A form without its UTF-8 part: what composes its bytes, and what the stages
+// before the copy grid run as.
+template <class Form>
+__host__ __device__ __forceinline__ auto plain_form(const Form& form)
+{
+    if constexpr (Form::kUtf8) return GatherForm{};
+    else return form;
+}
+template <class Form>
+using Plain = decltype(plain_form(std::declval<Form>()));
+static_assert(form_exists<EncodeForm>() && form_exists<GatherForm>() && form_exists<ReframeForm>() &&
+                  form_exists<Utf8GatherForm>(),
+              "encode, gather, reframe and validating gather: no other combination is written");
+
+// Frame f's flags word: read only where headers are written.
+template <class Form>
+__device__ __forceinline__ uint32_t flags_of(const Form& form, uint32_t f)
+{
+    if constexpr (Form::kHeaders) return form.flags[f];
+    else return 0u;
+}
+// Frame j's outgoing key: okeys[j] if its flags say masked (a NULL array:
+// every key 0), else 0; stored_key: whatever the flags say.
+template <class Form>
+__device__ __forceinline__ uint32_t out_key(const Form& form, uint32_t j, uint32_t fl)
+{
+    if constexpr (!Form::kReframe) return 0u;
+    else return ((fl >> 8) & 1u) != 0u && form.okeys != nullptr ? form.okeys[j] : 0u;
+}
+template <class Form>
+__device__ __forceinline__ uint32_t stored_key(const Form& form, uint32_t j)
+{
+    if constexpr (!Form::kReframe) return 0u;
+    else return form.okeys ? form.okeys[j] : 0u;
+}
+// The key the copy XORs (0 = none), from the descriptor's key and the outgoing key.
+template <class Form>
+__device__ __forceinline__ uint32_t copy_key(uint32_t key, uint32_t fl, uint32_t ok)
+{
+    const uint32_t mask = Form::kHeaders ? (fl >> 8) & 1u : 1u;
+    return Form::kReframe ? key ^ ok : (mask ? key : 0u);
 }
 // The key in a frame's header: the outgoing key, which is the copy's own key
 // in every form but the reframe.
-template <bool RF>
+template <class Form>
 __device__ __forceinline__ uint32_t hdr_key(uint32_t copy_key, uint32_t ok)
 {
-    return RF ? ok : copy_key;
+    return Form::kReframe ? ok : copy_key;
 }
 // A frame's region in the output: its header bytes and its payload bytes.
-template <bool HEADERS, bool RF>
+template <class Form>
 __device__ __forceinline__ uint32_t region_hdr(uint32_t len, uint32_t fl)
 {
-    if (RF && (fl & KMWS_FLAG_SKIP)) return 0u;
-    return HEADERS ? hdr_len(len, (fl >> 8) & 1u) : 0u;
+    if (Form::kReframe && (fl & KMWS_FLAG_SKIP)) return 0u;
+    return Form::kHeaders ? hdr_len(len, (fl >> 8) & 1u) : 0u;
 }
-template <bool RF>
+template <class Form>
 __device__ __forceinline__ uint32_t region_pay(uint32_t len, uint32_t fl)
 {
-    return RF && (fl & KMWS_FLAG_SKIP) ? 0u : len;
+    return Form::kReframe && (fl & KMWS_FLAG_SKIP) ? 0u : len;
 }
-template <bool HEADERS, bool RF>
+template <class Form>
 __device__ __forceinline__ uint64_t region_size(uint32_t len, uint32_t fl)
 {
-    return (uint64_t)region_hdr<HEADERS, RF>(len, fl) + region_pay<RF>(len, fl);
+    return (uint64_t)region_hdr<Form>(len, fl) + region_pay<Form>(len, fl);
 }
 
 // ------------------------------ scan ------------------------------
@@ -161,24 +248,20 @@ __host__ __device__ __forceinline__ uint64_t unit_bound(uint64_t R)
 struct SizeRaw {
     uint32_t len, fl;
 };
-struct WireSize {
-    static constexpr bool kHeaders = true;
+template <class Form>
+__device__ __forceinline__ V2 region_value(SizeRaw x)
+{
+    const uint64_t r = region_size<Form>(x.len, x.fl);
+    return V2{r, unit_bound(r)};
+}
+// A form's regions from the descriptors and, where it reads them, the flags.
+template <class Form>
+struct DescSize {
     static constexpr bool kClearsStatus = true;  // reduce_kernel clears the status word
     const kmws_desc* d;
-    const uint16_t* flags;
-    __device__ SizeRaw load(uint32_t f) const { return SizeRaw{d[f].len, flags[f]}; }
-    __device__ V2 value(SizeRaw x) const
-    {
-        const uint64_t r = (uint64_t)hdr_len(x.len, (x.fl >> 8) & 1u) + x.len;
-        return V2{r, unit_bound(r)};
-    }
-};
-struct PayloadSize {
-    static constexpr bool kHeaders = false;
-    static constexpr bool kClearsStatus = true;
-    const kmws_desc* d;
-    __device__ SizeRaw load(uint32_t f) const { return SizeRaw{d[f].len, 0u}; }
-    __device__ V2 value(SizeRaw x) const { return V2{x.len, unit_bound(x.len)}; }
+    Form form;
+    __device__ SizeRaw load(uint32_t f) const { return SizeRaw{d[f].len, flags_of(form, f)}; }
+    __device__ V2 value(SizeRaw x) const { return region_value<Form>(x); }
 };
 // The descriptor-indexed decode fused into the gather's scan
 // (kmws_unpack_gather): load() parses frame f's header where it lies in the
@@ -187,7 +270,6 @@ struct PayloadSize {
 // A header error ORs the status word during the kernel, so the word is
 // cleared by a launch before it, not by reduce_kernel.
 struct HeaderPayloadSize {
-    static constexpr bool kHeaders = false;
     static constexpr bool kClearsStatus = false;
     const uint8_t* wire;
     uint64_t wire_len;
@@ -203,21 +285,7 @@ struct HeaderPayloadSize {
         const kmws_desc o = unpack_one(wire, wire_len, hdr_off, n, f, mode, out_desc, out_flags, out_err, head);
         return SizeRaw{o.len, 0u};
     }
-    __device__ V2 value(SizeRaw x) const { return V2{x.len, unit_bound(x.len)}; }
-};
-
-// The reframe's regions from the descriptors and the outgoing flags.
-struct ReframeSize {
-    static constexpr bool kHeaders = true;
-    static constexpr bool kClearsStatus = true;
-    const kmws_desc* d;
-    const uint16_t* flags;
-    __device__ SizeRaw load(uint32_t f) const { return SizeRaw{d[f].len, flags[f]}; }
-    __device__ V2 value(SizeRaw x) const
-    {
-        const uint64_t r = region_size<true, true>(x.len, x.fl);
-        return V2{r, unit_bound(r)};
-    }
+    __device__ V2 value(SizeRaw x) const { return region_value<GatherForm>(x); }
 };
 // The parse fused into the reframe's scan (kmws_unpack_reframe): load() parses
 // frame f's header as HeaderPayloadSize does, derives the outgoing flags --
@@ -225,7 +293,6 @@ struct ReframeSize {
 // header error or an opcode outside relay_opcodes -- and writes them to the
 // workspace for the kernels that follow.
 struct HeaderReframeSize {
-    static constexpr bool kHeaders = true;
     static constexpr bool kClearsStatus = false;
     HeaderPayloadSize in;
     uint16_t* oflags;
@@ -242,11 +309,7 @@ struct HeaderReframeSize {
         oflags[f] = (uint16_t)fl;
         return SizeRaw{o.len, fl};
     }
-    __device__ V2 value(SizeRaw x) const
-    {
-        const uint64_t r = region_size<true, true>(x.len, x.fl);
-        return V2{r, unit_bound(r)};
-    }
+    __device__ V2 value(SizeRaw x) const { return region_value<ReframeForm>(x); }
 };
 
 __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x)
@@ -466,17 +529,16 @@ static_assert(sizeof(UnitRec) == 32, "UnitRec is one s_load_dwordx8");
 // Geometry of frame j given where its region starts (regions lie back to back:
 // frame j+1 starts where frame j's payload ends).
 // ok: the frame's outgoing key (out_key; the reframe only).
-template <bool HEADERS, bool RF>
+template <class Form>
 __device__ __forceinline__ FrameGeom geom_at(const kmws_desc& x, uint32_t fl, uint32_t ok, uint64_t r0)
 {
-    const uint32_t mask = HEADERS ? (fl >> 8) & 1u : 1u;
-    const uint32_t len = region_pay<RF>(x.len, fl);
+    const uint32_t len = region_pay<Form>(x.len, fl);
     FrameGeom g;
     g.r0 = r0;
-    g.p0 = r0 + region_hdr<HEADERS, RF>(x.len, fl);
+    g.p0 = r0 + region_hdr<Form>(x.len, fl);
     g.r1 = g.p0 + len;
     g.sdel = x.off - g.p0;
-    g.key = RF ? x.key ^ ok : (mask ? x.key : 0u);
+    g.key = copy_key<Form>(x.key, fl, ok);
     g.len = len;
     return g;
 }
@@ -485,21 +547,19 @@ __device__ __forceinline__ FrameGeom geom_at(const kmws_desc& x, uint32_t fl, ui
 // frame f overlaps in all but tiny-frame batches -- loaded at once (indices
 // clamped instead of branches, so the loads issue together).
 constexpr int kPre = 3;
-template <bool HEADERS, bool RF>
+template <class Form>
 __device__ __forceinline__ void load_descs(uint32_t f, uint32_t n, kmws_desc (&x)[kPre], uint32_t (&fl)[kPre],
-                                           uint32_t (&ok)[kPre], const kmws_desc* __restrict__ d,
-                                           const uint16_t* __restrict__ flags, const uint32_t* __restrict__ okeys)
+                                           uint32_t (&ok)[kPre], const kmws_desc* __restrict__ d, const Form& form)
 {
 #pragma unroll
     for (int i = 0; i < kPre; ++i) {
         const uint32_t j = f + i < n ? f + i : n - 1;
         x[i] = d[j];
-        fl[i] = HEADERS ? flags[j] : 0u;
-        ok[i] = 0u;
+        fl[i] = flags_of(form, j);
         // every stored key, whatever the flags say, so that the loads issue together
-        if constexpr (RF) ok[i] = okeys ? okeys[j] : 0u;
+        ok[i] = stored_key(form, j);
     }
-    if constexpr (RF) {
+    if constexpr (Form::kReframe) {
 #pragma unroll
         for (int i = 0; i < kPre; ++i) ok[i] = (fl[i] >> 8) & 1u ? ok[i] : 0u;
     }
@@ -508,30 +568,34 @@ __device__ __forceinline__ void load_descs(uint32_t f, uint32_t n, kmws_desc (&x
 // Output word [a, a + 16) composed byte by byte from every frame from f on that
 // overlaps it -- the rare word three or more regions reach into (frames shorter
 // than a word); few registers, one frame's geometry at a time (frame j+1's
-// region starts where frame j's ends).
-template <bool HEADERS, bool RF>
-__device__ __forceinline__ u32x4 compose_word_bytes_impl(uint64_t a, uint32_t f, uint32_t n,
-                                                         const uint8_t* __restrict__ src, FrameGeom h, uint32_t flj,
-                                                         const kmws_desc* __restrict__ d,
-                                                         const uint16_t* __restrict__ flags,
-                                                         const uint32_t* __restrict__ okeys)
+// region starts where frame j's ends; r0: where frame f's starts).
+// Out of line, with few enough arguments that the form, by value, travels in
+// registers (more, or by reference, and it would go through scratch).  The
+// validating gather's bytes are the gather's (plain_form).
+template <class Form>
+__device__ __attribute__((noinline)) u32x4 compose_word(uint64_t a, uint32_t f, uint32_t n,
+                                                        const uint8_t* __restrict__ src, uint64_t r0,
+                                                        const kmws_desc* __restrict__ d, Form form)
 {
+    static_assert(!Form::kUtf8, "composed as GatherForm");
     u32x4 out = u32x4{0, 0, 0, 0};
     uint32_t j = f;
-    uint32_t okj = out_key<RF>(okeys, f, flj);
+    uint32_t flj = flags_of(form, f);
+    uint32_t okj = out_key(form, f, flj);
+    FrameGeom h = geom_at<Form>(d[f], flj, okj, r0);
     for (uint32_t b = 0; b < 16; ++b) {
         const uint64_t x = a + b;
         while (x >= h.r1 && j + 1 < n) {
             ++j;
-            flj = HEADERS ? flags[j] : 0u;
-            okj = out_key<RF>(okeys, j, flj);
-            h = geom_at<HEADERS, RF>(d[j], flj, okj, h.r1);
+            flj = flags_of(form, j);
+            okj = out_key(form, j, flj);
+            h = geom_at<Form>(d[j], flj, okj, h.r1);
         }
         if (x < h.r0 || x >= h.r1) continue;  // past the last region
         uint32_t v;
         if (x < h.p0) {  // header byte x - r0
             uint64_t h0, h1;
-            build_header(h.len, flj, hdr_key<RF>(h.key, okj), h0, h1);
+            build_header(h.len, flj, hdr_key<Form>(h.key, okj), h0, h1);
             const uint32_t k = (uint32_t)(x - h.r0);
             v = (uint32_t)((k < 8 ? h0 >> (8 * k) : h1 >> (8 * (k - 8))) & 0xFFu);
         } else {  // payload byte: data[i] ^ key[i % 4]
@@ -544,30 +608,6 @@ __device__ __forceinline__ u32x4 compose_word_bytes_impl(uint64_t a, uint32_t f,
         else out.w |= v << sh;
     }
     return out;
-}
-template <bool HEADERS>
-__device__ __attribute__((noinline)) u32x4 compose_word_bytes(uint64_t a, uint32_t f, uint32_t n,
-                                                              const uint8_t* __restrict__ src, FrameGeom h,
-                                                              uint32_t flj, const kmws_desc* __restrict__ d,
-                                                              const uint16_t* __restrict__ flags)
-{
-    return compose_word_bytes_impl<HEADERS, false>(a, f, n, src, h, flj, d, flags, nullptr);
-}
-__device__ __attribute__((noinline)) u32x4 compose_word_bytes_reframe(uint64_t a, uint32_t f, uint32_t n,
-                                                                      const uint8_t* __restrict__ src, FrameGeom h,
-                                                                      uint32_t flj, const kmws_desc* __restrict__ d,
-                                                                      const uint16_t* __restrict__ flags,
-                                                                      const uint32_t* __restrict__ okeys)
-{
-    return compose_word_bytes_impl<true, true>(a, f, n, src, h, flj, d, flags, okeys);
-}
-template <bool HEADERS, bool RF>
-__device__ __forceinline__ u32x4 compose_word(uint64_t a, uint32_t f, uint32_t n, const uint8_t* __restrict__ src,
-                                              const FrameGeom& h, uint32_t flj, const kmws_desc* __restrict__ d,
-                                              const uint16_t* __restrict__ flags, const uint32_t* __restrict__ okeys)
-{
-    if constexpr (RF) return compose_word_bytes_reframe(a, f, n, src, h, flj, d, flags, okeys);
-    else return compose_word_bytes<HEADERS>(a, f, n, src, h, flj, d, flags);
 }
 
 // Payload source words of frame h for the output word [a, a + 16): the aligned
@@ -585,12 +625,12 @@ __device__ __forceinline__ void pay_words(bool live, const FrameGeom& h, uint64_
 
 // Frame h's bytes (header, then masked payload) in [a, a + 16), its payload
 // words W0/W1 from pay_words; hk: the key its header carries (hdr_key).
-template <bool HEADERS>
+template <class Form>
 __device__ __forceinline__ void put_frame(u32x4& out, uint64_t a, const FrameGeom& h, uint32_t fl, uint32_t hk,
                                           const u32x4& W0, const u32x4& W1)
 {
     if (h.r0 >= a + 16) return;
-    if (HEADERS && h.p0 > a && h.p0 > h.r0) {  // header bytes [r0, p0)
+    if (Form::kHeaders && h.p0 > a && h.p0 > h.r0) {  // header bytes [r0, p0)
         uint64_t h0, h1;
         build_header(h.len, fl, hk, h0, h1);
         const int s = (int)((int64_t)h.r0 - (int64_t)a);
@@ -608,19 +648,7 @@ __device__ __forceinline__ void put_frame(u32x4& out, uint64_t a, const FrameGeo
     }
 }
 
-// ---- the validating gather (kmws_gather_unmask_utf8) ----
-// What the validating forms of the copy kernels read besides the copy's own
-// arguments: each frame's view and the verdict words (kmws_utf8_dev.hpp), and
-// the frames in output space -- frame g is [start[g], start[g] + d[g].len).
-struct Utf8Gather {
-    const Utf8View* views;
-    uint32_t* first_bad;
-    const kmws_desc* d;
-    const uint64_t* start;
-    uint32_t n;
-};
-struct NoUtf8 {};
-
+// ---- the validating gather (Utf8GatherForm) ----
 // The output word v at output byte a against every checked frame from `g0` on
 // that has bytes in it -- the words that hold a frame edge (the unit form's
 // edge words, every word of chunk_dense_kernel).  The dword before the word is
@@ -628,7 +656,7 @@ struct NoUtf8 {};
 // from dst, which another wave may or may not have stored yet, and only where
 // the frame reaches back (word_bad uses no other byte of it).
 __device__ __forceinline__ void check_word_frames(const u32x4& v, uint64_t a, uint32_t g0,
-                                                  const uint8_t* __restrict__ src, const Utf8Gather& u)
+                                                  const uint8_t* __restrict__ src, const Utf8GatherForm& u)
 {
     for (uint32_t g = g0; g < u.n; ++g) {
         const uint64_t s = u.start[g];
@@ -697,14 +725,13 @@ struct RowInfo {
     uint64_t F0, S0, total;
     uint32_t nf;
 };
-template <bool HEADERS, bool RF>
+template <class Form>
 __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __restrict__ src,
-                                             const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                             const uint32_t* __restrict__ okeys, uint32_t n, uint64_t cap,
+                                             const kmws_desc* __restrict__ d, uint32_t n, uint64_t cap,
                                              WsHead* __restrict__ head,
                                              const V2* __restrict__ tiles, uint32_t ntiles,
                                              const V2* __restrict__ grp, uint64_t* __restrict__ start, RowLds& L,
-                                             RowInfo& ri)
+                                             RowInfo& ri, const Form& form)
 {
     FrameUnits* s_fu = L.fu;
     uint32_t* s_ub = L.ub;
@@ -721,10 +748,10 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
     const uint64_t total = tot.a;
     kmws_desc x[kPre];
     uint32_t fl[kPre], ok[kPre];
-    load_descs<HEADERS, RF>(f, n, x, fl, ok, d, flags, okeys);
+    load_descs(f, n, x, fl, ok, d, form);
     // this frame's region offset and first unit slot
     V2 row;
-    const uint64_t rsz = region_size<HEADERS, RF>(x[0].len, fl[0]);
+    const uint64_t rsz = region_size<Form>(x[0].len, fl[0]);
     const V2 off = pre + block_excl_scan(t < nf ? V2{rsz, unit_bound(rsz)} : V2{0, 0}, s_w, row);
     const uint64_t r0 = off.a, uf = off.b, S0 = pre.b, uend = pre.b + row.b;
     if (t < nf) start[f] = r0;
@@ -737,10 +764,10 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
         return false;
     }
     FrameGeom g[kPre];
-    g[0] = geom_at<HEADERS, RF>(x[0], fl[0], ok[0], r0);
+    g[0] = geom_at<Form>(x[0], fl[0], ok[0], r0);
 #pragma unroll
     for (int i = 1; i < kPre; ++i) {
-        g[i] = geom_at<HEADERS, RF>(x[i], fl[i], ok[i], g[i - 1].r1);
+        g[i] = geom_at<Form>(x[i], fl[i], ok[i], g[i - 1].r1);
         if ((uint64_t)f + i >= n) g[i].r0 = ~0ull;  // past the last frame: overlaps nothing
     }
     if (t < nf) {
@@ -792,7 +819,7 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
                 third |= 1u;
             } else {
                 u32x4 out = u32x4{0, 0, 0, 0};
-                put_frame<HEADERS>(out, ah, F, fl[0], hdr_key<RF>(F.key, ok[0]), H0, H1);
+                put_frame<Form>(out, ah, F, fl[0], hdr_key<Form>(F.key, ok[0]), H0, H1);
                 my[0] = out;
             }
         }
@@ -807,11 +834,11 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
                 continue;
             }
             u32x4 out = u32x4{0, 0, 0, 0};
-            if (i == 0) put_frame<HEADERS>(out, a, F, fl[0], hdr_key<RF>(F.key, ok[0]), T0, T1);
+            if (i == 0) put_frame<Form>(out, a, F, fl[0], hdr_key<Form>(F.key, ok[0]), T0, T1);
             if (N.r0 < a + 16) {
-                if (HEADERS && N.p0 > a && N.p0 > N.r0) {  // f+1's header bytes [r0, p0)
+                if (Form::kHeaders && N.p0 > a && N.p0 > N.r0) {  // f+1's header bytes [r0, p0)
                     uint64_t h0, h1;
-                    build_header(N.len, fl[1], hdr_key<RF>(N.key, ok[1]), h0, h1);
+                    build_header(N.len, fl[1], hdr_key<Form>(N.key, ok[1]), h0, h1);
                     const int sh = (int)((int64_t)N.r0 - (int64_t)a);
                     const u32x4 Hw = u32x4{(uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32)};
                     const int he = (int)(N.p0 - N.r0) + sh;
@@ -828,7 +855,7 @@ __device__ __forceinline__ bool row_prologue(uint32_t rid, const uint8_t* __rest
         for (int q = 0; third != 0; ++q, third >>= 1) {
             if (third & 1u) {
                 const uint64_t a = 16u * ((uint32_t)q < head_f ? w.olo + q : w.ihi + (q - head_f));
-                my[q] = compose_word<HEADERS, RF>(a, f, n, src, g[0], fl[0], d, flags, okeys);
+                my[q] = compose_word(a, f, n, src, r0, d, form);
             }
         }
     }
@@ -856,19 +883,18 @@ __device__ __forceinline__ UnitRec make_rec(const FrameUnits& fu, uint32_t m, ui
     return r;
 }
 
-template <bool HEADERS, bool RF>
-__device__ __forceinline__ void prologue_body(const uint8_t* src, const kmws_desc* d,
-                                              const uint16_t* flags, const uint32_t* okeys,
-                                              uint32_t n, uint64_t cap, WsHead* head,
-                                              const V2* tiles, uint32_t ntiles,
-                                              const V2* grp, uint64_t* start,
-                                              UnitRec* rec, u32x4* edge)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) prologue_kernel(const uint8_t* __restrict__ src,
+                                                          const kmws_desc* __restrict__ d, uint32_t n, uint64_t cap,
+                                                          WsHead* __restrict__ head, const V2* __restrict__ tiles,
+                                                          uint32_t ntiles, const V2* __restrict__ grp,
+                                                          uint64_t* __restrict__ start, UnitRec* __restrict__ rec,
+                                                          u32x4* __restrict__ edge, Form form)
 {
     __shared__ RowLds L;
     RowInfo ri;
     const uint32_t t = threadIdx.x;
-    if (!row_prologue<HEADERS, RF>(blockIdx.x, src, d, flags, okeys, n, cap, head, tiles, ntiles, grp, start, L, ri))
-        return;
+    if (!row_prologue(blockIdx.x, src, d, n, cap, head, tiles, ntiles, grp, start, L, ri, form)) return;
     const uint64_t F0 = ri.F0, S0 = ri.S0;
     const uint32_t nf = ri.nf;
     const FrameUnits* s_fu = L.fu;
@@ -911,32 +937,6 @@ __device__ __forceinline__ void prologue_body(const uint8_t* src, const kmws_des
     }
 }
 
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) prologue_kernel(const uint8_t* __restrict__ src,
-                                                          const kmws_desc* __restrict__ d,
-                                                          const uint16_t* __restrict__ flags, uint32_t n,
-                                                          uint64_t cap, WsHead* __restrict__ head,
-                                                          const V2* __restrict__ tiles, uint32_t ntiles,
-                                                          const V2* __restrict__ grp, uint64_t* __restrict__ start,
-                                                          UnitRec* __restrict__ rec, u32x4* __restrict__ edge)
-{
-    prologue_body<HEADERS, false>(src, d, flags, nullptr, n, cap, head, tiles, ntiles, grp, start, rec, edge);
-}
-
-// The reframe's prologue; its unit records and edge words go to copy_kernel<true>.
-__global__ void __launch_bounds__(kBlock) prologue_reframe_kernel(const uint8_t* __restrict__ src,
-                                                                  const kmws_desc* __restrict__ d,
-                                                                  const uint16_t* __restrict__ flags,
-                                                                  const uint32_t* __restrict__ okeys, uint32_t n,
-                                                                  uint64_t cap, WsHead* __restrict__ head,
-                                                                  const V2* __restrict__ tiles, uint32_t ntiles,
-                                                                  const V2* __restrict__ grp,
-                                                                  uint64_t* __restrict__ start,
-                                                                  UnitRec* __restrict__ rec, u32x4* __restrict__ edge)
-{
-    prologue_body<true, true>(src, d, flags, okeys, n, cap, head, tiles, ntiles, grp, start, rec, edge);
-}
-
 __device__ __forceinline__ u32x4 shfl16(const u32x4& v, int lane)
 {
     return u32x4{(uint32_t)__shfl((int)v.x, lane, 64), (uint32_t)__shfl((int)v.y, lane, 64),
@@ -974,7 +974,7 @@ __device__ __forceinline__ UnitInfo decode_unit(const UnitRec& r, bool live, con
 // shifted source run of 1 KiB per wave instruction starts mid-line, so two
 // instructions (or two waves) share its edge lines.
 constexpr int kUnitW = kUnitWords / 64;  // words per lane
-static_assert(kUnitW == 4, "copy_body selects an edge word among four");
+static_assert(kUnitW == 4, "copy_kernel selects an edge word among four");
 struct UnitRegs {
     u32x4 lo[kUnitW];  // aligned source word of each of the lane's output words
     u32x4 ex;          // the source word after the last interior word (every lane: one address)
@@ -1123,19 +1123,25 @@ __device__ __forceinline__ void prev_dwords(const u32x4 (&out)[W], int lane, uin
 }
 
 // One wave per unit: kUnitW words per lane, 1 KiB per wave-instruction.
-// UTF8 (the validating gather): the unit's words are stored exactly as without
+// A unit's record and edge words hold everything of its form but the UTF-8
+// part, so the kernel is instantiated on that alone: GatherForm (every form
+// that checks nothing) and Utf8GatherForm.
+// kUtf8 (the validating gather): the unit's words are stored exactly as without
 // it; then the words of checked frames are validated from the registers that
 // hold them, in output space.  Interior words belong to the unit's frame
 // (wave-uniform: its start, length and view are scalar loads issued ahead of
 // the payload); edge words walk their frames (check_word_frames).  The dword
 // before the unit's first owned word comes from the source (lookback_issue).
 // A unit of an unchecked frame without edge words ends after its stores.
-template <bool HEADERS, bool UTF8, class U>
-__device__ __forceinline__ void copy_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                          const V2* __restrict__ tot, const UnitRec* __restrict__ rec,
-                                          const u32x4* __restrict__ edge, const WsHead* __restrict__ head,
-                                          uint64_t unit_base, uint32_t split, const U& ug)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                      const V2* __restrict__ tot,
+                                                      const UnitRec* __restrict__ rec,
+                                                      const u32x4* __restrict__ edge,
+                                                      const WsHead* __restrict__ head, uint64_t unit_base,
+                                                      uint32_t split, Form ug)
 {
+    static_assert(!Form::kHeaders && !Form::kReframe, "the unit copy reads the form's UTF-8 part only");
     const int lane = threadIdx.x & 63;
     // wave id through readfirstlane: provably uniform, so the record is one scalar load
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1168,11 +1174,10 @@ __device__ __forceinline__ void copy_body(const uint8_t* __restrict__ src, uint8
     // Every load is issued before the first store (vmcnt also counts stores, so
     // a load issued after a store would make its wait cover that store too).
     UnitRegs R;
-    if constexpr (!UTF8) {
+    if constexpr (!Form::kUtf8) {
         unit_issue(x, lane, src, edge + (uint64_t)x.f * kEdgeWords, R);
         unit_finish(x, lane, dst, total, R);
     } else {
-        static_assert(!HEADERS, "the validating form is the gather's");
         // the frame in output space and its view: scalar loads, in flight under the payload's
         const uint64_t fs = ug.start[x.f];
         const uint32_t flen = ug.d[x.f].len;
@@ -1214,30 +1219,6 @@ __device__ __forceinline__ void copy_body(const uint8_t* __restrict__ src, uint8
     }
 }
 
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                      const V2* __restrict__ tot,
-                                                      const UnitRec* __restrict__ rec,
-                                                      const u32x4* __restrict__ edge,
-                                                      const WsHead* __restrict__ head, uint64_t unit_base,
-                                                      uint32_t split)
-{
-    copy_body<HEADERS, false>(src, dst, tot, rec, edge, head, unit_base, split, NoUtf8{});
-}
-
-// Registers ("the validating gather"): 98 VGPRs, 4 waves per SIMD, no
-// scratch.  Asking the allocator for the 5 waves per SIMD that the large-frame
-// launches' dynamic LDS allows costs 12 B of scratch per lane.
-__global__ void __launch_bounds__(kBlock) copy_utf8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                           const V2* __restrict__ tot,
-                                                           const UnitRec* __restrict__ rec,
-                                                           const u32x4* __restrict__ edge,
-                                                           const WsHead* __restrict__ head, uint64_t unit_base,
-                                                           uint32_t split, Utf8Gather u)
-{
-    copy_body<false, true>(src, dst, tot, rec, edge, head, unit_base, split, u);
-}
-
 __device__ __forceinline__ u32x4 shfl16_down1(const u32x4& v)
 {
     return u32x4{(uint32_t)__shfl_down((int)v.x, 1, 64), (uint32_t)__shfl_down((int)v.y, 1, 64),
@@ -1267,7 +1248,7 @@ constexpr uint64_t kChunkBytes = 16ull * kChunkWords;
 constexpr uint32_t kSlowShift = 9;  // boundary-list entry: word | table frame << kSlowShift
 constexpr uint32_t kSlowWord = (1u << kSlowShift) - 1;
 static_assert(kChunkW == 4 || kChunkW == 8, "chunk: 4 or 8 words per lane");
-static_assert(kChunkW == 4, "chunk_body (the validating form) selects a word among four");
+static_assert(kChunkW == 4, "chunk_copy_kernel (the validating form) selects a word among four");
 constexpr uint32_t kChunkFrames = 64;           // a chunk's frame table, one lane per frame
 
 __host__ __device__ __forceinline__ uint64_t chunk_count(uint64_t bytes) { return (bytes + kChunkBytes - 1) / kChunkBytes; }
@@ -1275,12 +1256,12 @@ __host__ __device__ __forceinline__ uint64_t chunk_count(uint64_t bytes) { retur
 // 256 frames per block, after the scan: each frame's region offset (start[f])
 // and, for every chunk whose first byte lies in the block's regions, the frame
 // holding it (cmap[c]).  Also the capacity check (status set, nothing stored).
-template <bool HEADERS, bool RF>
-__device__ __forceinline__ void chunk_map_body(const kmws_desc* d, const uint16_t* flags,
-                                               uint32_t n, uint64_t cap, WsHead* head,
-                                               const V2* tiles, uint32_t ntiles,
-                                               const V2* grp, uint64_t* start,
-                                               uint32_t* cmap)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __restrict__ d, uint32_t n, uint64_t cap,
+                                                           WsHead* __restrict__ head, const V2* __restrict__ tiles,
+                                                           uint32_t ntiles, const V2* __restrict__ grp,
+                                                           uint64_t* __restrict__ start, uint32_t* __restrict__ cmap,
+                                                           Form form)
 {
     __shared__ uint64_t s_r0[kBlock + 1];
     __shared__ V2 s_w[kBlock / 64];
@@ -1291,8 +1272,8 @@ __device__ __forceinline__ void chunk_map_body(const kmws_desc* d, const uint16_
     const V2 tot = tiles[ntiles];
     const V2 pre = tiles[blockIdx.x / kRowsPerTile] + grp[blockIdx.x];
     const kmws_desc x = d[f];
-    const uint32_t fl = HEADERS ? flags[f] : 0u;
-    const uint64_t rsz = region_size<HEADERS, RF>(x.len, fl);
+    const uint32_t fl = flags_of(form, f);
+    const uint64_t rsz = region_size<Form>(x.len, fl);
     if (blockIdx.x == 0 && t == 0) head->pad[0] = 0;  // chunk_copy_kernel's dense-chunk count
     V2 row;
     const V2 off = block_excl_scan(t < nf ? V2{rsz, 0} : V2{0, 0}, s_w, row);
@@ -1317,27 +1298,6 @@ __device__ __forceinline__ void chunk_map_body(const kmws_desc* d, const uint16_
         }
         cmap[c] = (uint32_t)F0 + lo;
     }
-}
-
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_map_kernel(const kmws_desc* __restrict__ d,
-                                                           const uint16_t* __restrict__ flags, uint32_t n, uint64_t cap,
-                                                           WsHead* __restrict__ head, const V2* __restrict__ tiles,
-                                                           uint32_t ntiles, const V2* __restrict__ grp,
-                                                           uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
-{
-    chunk_map_body<HEADERS, false>(d, flags, n, cap, head, tiles, ntiles, grp, start, cmap);
-}
-
-__global__ void __launch_bounds__(kBlock) chunk_map_reframe_kernel(const kmws_desc* __restrict__ d,
-                                                                   const uint16_t* __restrict__ flags, uint32_t n,
-                                                                   uint64_t cap, WsHead* __restrict__ head,
-                                                                   const V2* __restrict__ tiles, uint32_t ntiles,
-                                                                   const V2* __restrict__ grp,
-                                                                   uint64_t* __restrict__ start,
-                                                                   uint32_t* __restrict__ cmap)
-{
-    chunk_map_body<true, true>(d, flags, n, cap, head, tiles, ntiles, grp, start, cmap);
 }
 
 // One frame of a chunk's table (LDS), 48 B: its geometry relative to the
@@ -1393,7 +1353,7 @@ __device__ __forceinline__ u32x4 copy_src_load(const uint8_t* p)
 
 // One wave per 4 KiB output chunk (4 words per lane, 1 KiB per instruction).
 // A chunk meeting more than kChunkFrames frames is listed for chunk_dense_kernel.
-// UTF8 (the validating gather): each frame's view rides in its table entry
+// kUtf8 (the validating gather): each frame's view rides in its table entry
 // (loaded with its descriptor), so after the four stores the rule reads
 // registers and LDS only; a chunk whose frames are all unchecked ends after the
 // stores.  Interior words run the word test against their one frame, boundary
@@ -1401,15 +1361,16 @@ __device__ __forceinline__ u32x4 copy_src_load(const uint8_t* p)
 // chunk's first word comes from the source (lookback_issue).  A chunk with more
 // than 64 boundary words (whose surplus is stored from LDS, not from the
 // registers validated here) goes to chunk_dense_kernel as well.
-template <bool HEADERS, bool UTF8, bool RF, class U>
-__device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                           const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                           const uint32_t* __restrict__ okeys, uint32_t n,
-                                           const uint64_t* __restrict__ start,
-                                           const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
-                                           WsHead* __restrict__ head, uint32_t* __restrict__ dense,
-                                           uint64_t chunk_base, uint32_t split, const U& u)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                            const kmws_desc* __restrict__ d, uint32_t n,
+                                                            const uint64_t* __restrict__ start,
+                                                            const uint32_t* __restrict__ cmap,
+                                                            const V2* __restrict__ tot, WsHead* __restrict__ head,
+                                                            uint32_t* __restrict__ dense, uint64_t chunk_base,
+                                                            uint32_t split, Form form)
 {
+    constexpr bool kUtf8 = Form::kUtf8;
     __shared__ ChunkFrame s_tab[kBlock / 64][kChunkFrames];
     __shared__ uint16_t s_slow[kBlock / 64][kChunkWords];  // boundary words: word | frame << kSlowShift
     __shared__ u32x4 s_val[kBlock / 64][64 + 16];  // boundary words 0..63, then 16 scratch slots
@@ -1439,23 +1400,22 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
     if ((uint32_t)lane < nfr) {
         const uint32_t j = f0 + lane;
         const kmws_desc x = d[j];
-        const uint32_t fl = HEADERS ? flags[j] : 0u;
-        const uint32_t mask = HEADERS ? (fl >> 8) & 1u : 1u;
-        const uint32_t ok = out_key<RF>(okeys, j, fl);
-        const uint64_t r0 = start[j], p0 = r0 + region_hdr<HEADERS, RF>(x.len, fl);
-        const uint32_t key = RF ? x.key ^ ok : (mask ? x.key : 0u);
+        const uint32_t fl = flags_of(form, j);
+        const uint32_t ok = out_key(form, j, fl);
+        const uint64_t r0 = start[j], p0 = r0 + region_hdr<Form>(x.len, fl);
+        const uint32_t key = copy_key<Form>(x.key, fl, ok);
         ChunkFrame e;
         e.r0 = rel32(r0, A0);
         e.p0 = rel32(p0, A0);
-        e.r1 = rel32(p0 + region_pay<RF>(x.len, fl), A0);
+        e.r1 = rel32(p0 + region_pay<Form>(x.len, fl), A0);
         e.rk = key ? rot_key(key, p0) : 0u;
         e.sbase = (uint64_t)(uintptr_t)src + x.off - (p0 - A0);
         uint64_t h0 = 0, h1 = 0;
-        if (HEADERS) build_header(x.len, fl, hdr_key<RF>(key, ok), h0, h1);
+        if (Form::kHeaders) build_header(x.len, fl, hdr_key<Form>(key, ok), h0, h1);
         __builtin_memcpy(e.h, &h0, 8);
         __builtin_memcpy(e.h + 8, &h1, 8);
-        if constexpr (UTF8) {
-            const Utf8View gv = u.views[j];
+        if constexpr (kUtf8) {
+            const Utf8View gv = form.views[j];
             e.pad = (uint64_t)gv.slot | (uint64_t)gv.w << 32;
             chk_lane = (gv.w & kUtf8Checked) != 0u && x.len != 0u;
         }
@@ -1498,7 +1458,7 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
         nslow += (uint32_t)__builtin_popcountll(bal);
     }
     wave_lds_sync();
-    if constexpr (UTF8) {
+    if constexpr (kUtf8) {
         if (nslow > 64u) {  // wave-uniform
             if (lane == 0) dense[atomicAdd(&head->pad[0], 1u)] = (uint32_t)c;
             return;
@@ -1523,7 +1483,7 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
             while (m + 1 < nfr && tab[m + 1].r0 <= x) ++m;
             const ChunkFrame& e = tab[m];
             const bool live = qi < nslow && x < trel;
-            const bool hdr = HEADERS && x < e.p0;
+            const bool hdr = Form::kHeaders && x < e.p0;
             if (hdr)  // header byte x - r0 (< 14); bit 8: no source byte
                 hv[u] = 0x100u | e.h[live ? (uint32_t)(x - e.r0) & 15u : 0u];
             else  // the key byte of output byte x
@@ -1568,7 +1528,7 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
     }
     X = copy_src_load(reinterpret_cast<const uint8_t*>(xa));
     uint32_t lb = 0;
-    if constexpr (UTF8) {  // output bytes -4 .. -1 where the chunk's first frame holds them
+    if constexpr (kUtf8) {  // output bytes -4 .. -1 where the chunk's first frame holds them
         const ChunkFrame& e0 = tab[0];
         lb = lookback_issue(reinterpret_cast<const uint8_t*>(e0.sbase), lane - 4 >= e0.p0 && e0.r1 > 0, lane);
     }
@@ -1582,7 +1542,7 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
     // the look-back dword is taken before the first store: a wait for its load
     // behind them would wait for the stores as well
     uint32_t edge_dw = 0;
-    if constexpr (UTF8) edge_dw = lookback_dword(lb, tab[0].rk);
+    if constexpr (kUtf8) edge_dw = lookback_dword(lb, tab[0].rk);
     // Pass 4: the four full-width stores, boundary words merged in.
     uint32_t seen = 0;
     u32x4 outv[kChunkW];
@@ -1612,7 +1572,7 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
         else if (mine && a < total) store_word_bytes(dst, a, total, out);
         outv[i] = out;
     }
-    if constexpr (UTF8) {
+    if constexpr (kUtf8) {
         if (__ballot(chk_lane) == 0ull) return;  // wave-uniform: binary, RSV1 and control frames end here
         uint32_t prev[kChunkW];
         prev_dwords<(int)kChunkW>(outv, lane, 0u, edge_dw, prev);
@@ -1654,70 +1614,26 @@ __device__ __forceinline__ void chunk_body(const uint8_t* __restrict__ src, uint
                 if (e.r1 <= e.p0 || e.r1 <= a || !(vw & kUtf8Checked)) continue;
                 if (plain_word_frame_bad(w, pv, (uint64_t)(a + kBias), (uint64_t)(e.p0 + kBias),
                                          (uint64_t)(e.r1 + kBias), vw))
-                    report_bad(u.first_bad, (uint32_t)e.pad, f0 + m);
+                    report_bad(form.first_bad, (uint32_t)e.pad, f0 + m);
             }
         }
     }
-}
-
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                            const kmws_desc* __restrict__ d,
-                                                            const uint16_t* __restrict__ flags, uint32_t n,
-                                                            const uint64_t* __restrict__ start,
-                                                            const uint32_t* __restrict__ cmap,
-                                                            const V2* __restrict__ tot, WsHead* __restrict__ head,
-                                                            uint32_t* __restrict__ dense, uint64_t chunk_base,
-                                                            uint32_t split)
-{
-    chunk_body<HEADERS, false, false>(src, dst, d, flags, nullptr, n, start, cmap, tot, head, dense, chunk_base, split,
-                                      NoUtf8{});
-}
-
-// Registers: see DESIGN 4 ("the reframe").
-__global__ void __launch_bounds__(kBlock) chunk_copy_reframe_kernel(const uint8_t* __restrict__ src,
-                                                                    uint8_t* __restrict__ dst,
-                                                                    const kmws_desc* __restrict__ d,
-                                                                    const uint16_t* __restrict__ flags,
-                                                                    const uint32_t* __restrict__ okeys, uint32_t n,
-                                                                    const uint64_t* __restrict__ start,
-                                                                    const uint32_t* __restrict__ cmap,
-                                                                    const V2* __restrict__ tot,
-                                                                    WsHead* __restrict__ head,
-                                                                    uint32_t* __restrict__ dense, uint64_t chunk_base,
-                                                                    uint32_t split)
-{
-    chunk_body<true, false, true>(src, dst, d, flags, okeys, n, start, cmap, tot, head, dense, chunk_base, split,
-                                  NoUtf8{});
-}
-
-// Registers: see DESIGN 4 ("the validating gather").
-__global__ void __launch_bounds__(kBlock) chunk_copy_utf8_kernel(const uint8_t* __restrict__ src,
-                                                                 uint8_t* __restrict__ dst,
-                                                                 const kmws_desc* __restrict__ d, uint32_t n,
-                                                                 const uint64_t* __restrict__ start,
-                                                                 const uint32_t* __restrict__ cmap,
-                                                                 const V2* __restrict__ tot, WsHead* __restrict__ head,
-                                                                 uint32_t* __restrict__ dense, uint64_t chunk_base,
-                                                                 uint32_t split, Utf8Gather u)
-{
-    chunk_body<false, true, false>(src, dst, d, nullptr, nullptr, n, start, cmap, tot, head, dense, chunk_base, split, u);
 }
 
 // The chunks chunk_copy_kernel listed (more than kChunkFrames frames: regions
 // averaging under 64 bytes): every word byte by byte, its first frame by a
 // binary search over start[].  Correct for any batch, fast only where it does
 // not matter; a batch of small frames takes the unit form instead (below).
-// UTF8 (the validating gather): every word is also checked against the frames
+// kUtf8 (the validating gather): every word is also checked against the frames
 // in it (check_word_frames).
-template <bool HEADERS, bool UTF8, bool RF, class U>
-__device__ __forceinline__ void dense_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                           const kmws_desc* __restrict__ d, const uint16_t* __restrict__ flags,
-                                           const uint32_t* __restrict__ okeys, uint32_t n,
-                                           const uint64_t* __restrict__ start,
-                                           const uint32_t* __restrict__ cmap, const V2* __restrict__ tot,
-                                           const WsHead* __restrict__ head, const uint32_t* __restrict__ dense,
-                                           const U& u)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                             const kmws_desc* __restrict__ d, uint32_t n,
+                                                             const uint64_t* __restrict__ start,
+                                                             const uint32_t* __restrict__ cmap,
+                                                             const V2* __restrict__ tot,
+                                                             const WsHead* __restrict__ head,
+                                                             const uint32_t* __restrict__ dense, Form form)
 {
     if (head->status & (kStatusBadDesc | kStatusLookbackTimeout)) return;
     const uint32_t cnt = head->pad[0];
@@ -1735,53 +1651,12 @@ __device__ __forceinline__ void dense_body(const uint8_t* __restrict__ src, uint
                 const uint32_t mid = (lo + hi) >> 1;
                 if (start[mid] <= a) lo = mid; else hi = mid;
             }
-            const uint32_t fl = HEADERS ? flags[lo] : 0u;
-            const FrameGeom g = geom_at<HEADERS, RF>(d[lo], fl, out_key<RF>(okeys, lo, fl), start[lo]);
-            const u32x4 v = compose_word<HEADERS, RF>(a, lo, n, src, g, fl, d, flags, okeys);
+            const u32x4 v = compose_word(a, lo, n, src, start[lo], d, plain_form(form));
             if (a + 16 <= total) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst + a));
             else store_word_bytes(dst, a, total, v);
-            if constexpr (UTF8) check_word_frames(v, a, lo, src, u);
+            if constexpr (Form::kUtf8) check_word_frames(v, a, lo, src, form);
         }
     }
-}
-
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_dense_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                             const kmws_desc* __restrict__ d,
-                                                             const uint16_t* __restrict__ flags, uint32_t n,
-                                                             const uint64_t* __restrict__ start,
-                                                             const uint32_t* __restrict__ cmap,
-                                                             const V2* __restrict__ tot,
-                                                             const WsHead* __restrict__ head,
-                                                             const uint32_t* __restrict__ dense)
-{
-    dense_body<HEADERS, false, false>(src, dst, d, flags, nullptr, n, start, cmap, tot, head, dense, NoUtf8{});
-}
-
-__global__ void __launch_bounds__(kBlock) chunk_dense_reframe_kernel(const uint8_t* __restrict__ src,
-                                                                     uint8_t* __restrict__ dst,
-                                                                     const kmws_desc* __restrict__ d,
-                                                                     const uint16_t* __restrict__ flags,
-                                                                     const uint32_t* __restrict__ okeys, uint32_t n,
-                                                                     const uint64_t* __restrict__ start,
-                                                                     const uint32_t* __restrict__ cmap,
-                                                                     const V2* __restrict__ tot,
-                                                                     const WsHead* __restrict__ head,
-                                                                     const uint32_t* __restrict__ dense)
-{
-    dense_body<true, false, true>(src, dst, d, flags, okeys, n, start, cmap, tot, head, dense, NoUtf8{});
-}
-
-__global__ void __launch_bounds__(kBlock) chunk_dense_utf8_kernel(const uint8_t* __restrict__ src,
-                                                                  uint8_t* __restrict__ dst,
-                                                                  const kmws_desc* __restrict__ d, uint32_t n,
-                                                                  const uint64_t* __restrict__ start,
-                                                                  const uint32_t* __restrict__ cmap,
-                                                                  const V2* __restrict__ tot,
-                                                                  const WsHead* __restrict__ head,
-                                                                  const uint32_t* __restrict__ dense, Utf8Gather u)
-{
-    dense_body<false, true, false>(src, dst, d, nullptr, nullptr, n, start, cmap, tot, head, dense, u);
 }
 
 // ------------------------------ header unpack / validate ------------------------------
@@ -2037,11 +1912,11 @@ __global__ void __launch_bounds__(kBlock) zero_words_kernel(uint64_t* __restrict
 // dense count are zeroed by the launch before it.  The last tile writes the
 // total (start[n] and tot) and the capacity check; every tile clips its chunk
 // map to the capacity, so an oversized batch writes nothing out of bounds.
-template <bool HEADERS, bool RF>
-__device__ __forceinline__ void chunk_scan_body(const kmws_desc* d, const uint16_t* flags,
-                                                uint32_t n, uint64_t cap, WsHead* head,
-                                                uint64_t* st, V2* tot,
-                                                uint64_t* start, uint32_t* cmap)
+template <class Form>
+__global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __restrict__ d, uint32_t n, uint64_t cap,
+                                                            WsHead* __restrict__ head, uint64_t* __restrict__ st,
+                                                            V2* __restrict__ tot, uint64_t* __restrict__ start,
+                                                            uint32_t* __restrict__ cmap, Form form)
 {
     __shared__ uint64_t s_sz[kScanTile];  // region sizes, then offsets
     __shared__ uint64_t s_w[kBlock / 64];
@@ -2056,13 +1931,13 @@ __device__ __forceinline__ void chunk_scan_body(const kmws_desc* d, const uint16
         const uint64_t f = F + (uint64_t)i * kBlock + t;
         const uint32_t j = (uint32_t)__builtin_elementwise_min(f, (uint64_t)n - 1);
         len[i] = d[j].len;
-        fl[i] = HEADERS ? flags[j] : 0u;
+        fl[i] = flags_of(form, j);
     }
     uint64_t part = 0;
 #pragma unroll
     for (int i = 0; i < kScanItems; ++i) {
         const uint64_t f = F + (uint64_t)i * kBlock + t;
-        const uint64_t r = region_size<HEADERS, RF>(len[i], fl[i]);
+        const uint64_t r = region_size<Form>(len[i], fl[i]);
         part += f < n ? r : 0;
         s_sz[i * kBlock + t] = f < n ? r : 0;
     }
@@ -2127,26 +2002,6 @@ __device__ __forceinline__ void chunk_scan_body(const kmws_desc* d, const uint16
         }
         cmap[c] = (uint32_t)(F + lo);
     }
-}
-
-template <bool HEADERS>
-__global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const kmws_desc* __restrict__ d,
-                                                            const uint16_t* __restrict__ flags, uint32_t n,
-                                                            uint64_t cap, WsHead* __restrict__ head,
-                                                            uint64_t* __restrict__ st, V2* __restrict__ tot,
-                                                            uint64_t* __restrict__ start, uint32_t* __restrict__ cmap)
-{
-    chunk_scan_body<HEADERS, false>(d, flags, n, cap, head, st, tot, start, cmap);
-}
-
-__global__ void __launch_bounds__(kBlock) chunk_scan_reframe_kernel(const kmws_desc* __restrict__ d,
-                                                                    const uint16_t* __restrict__ flags, uint32_t n,
-                                                                    uint64_t cap, WsHead* __restrict__ head,
-                                                                    uint64_t* __restrict__ st, V2* __restrict__ tot,
-                                                                    uint64_t* __restrict__ start,
-                                                                    uint32_t* __restrict__ cmap)
-{
-    chunk_scan_body<true, true>(d, flags, n, cap, head, st, tot, start, cmap);
 }
 
 // ------------------------------ header-chain walk, many streams ------------------------------
@@ -2264,10 +2119,13 @@ struct CopyWs {
     uint32_t* dense;  // chunks chunk_copy_kernel left to chunk_dense_kernel
 };
 
-// The validating gather's per-frame kernels (kmws_utf8.hip) run on the source
-// right before the copy grid -- after whatever cleared the status word and, in
-// the unpack form, wrote the descriptors and flags -- and its finish after it.
+// The validating gather's form as the host holds it: the device part
+// (Utf8GatherForm) exists only once its per-frame kernels (kmws_utf8.hip) have
+// run on the source, right before the copy grid -- after whatever cleared the
+// status word and, in the unpack form, wrote the descriptors and flags -- and
+// its finish runs after the grid.  The stages before it run as GatherForm.
 struct Utf8Launch {
+    static constexpr bool kHeaders = false, kReframe = false, kUtf8 = true;
     void* arrays;  // utf8_frame_arrays_size(n, n_streams) bytes
     const uint16_t* flags;
     uint64_t span;  // of the source: descriptors past it set status bit 1
@@ -2277,12 +2135,12 @@ struct Utf8Launch {
     kmws_utf8_carry* carry_out;
     uint8_t* out;
 };
-static Utf8Gather launch_utf8_before_copy(const Utf8Launch& ul, WsHead* head, const uint8_t* src, const kmws_desc* d,
-                                          const uint64_t* start, uint32_t n, hipStream_t s)
+static Utf8GatherForm launch_utf8_before_copy(const Utf8Launch& ul, WsHead* head, const uint8_t* src,
+                                              const kmws_desc* d, const uint64_t* start, uint32_t n, hipStream_t s)
 {
     const Utf8FrameArrays fa = launch_utf8_frame_state(ul.arrays, head, src, ul.span, d, ul.flags, n, 1,
                                                        ul.stream_first, ul.n_streams, ul.carry_in, s);
-    return Utf8Gather{fa.views, fa.first_bad, d, start, n};
+    return Utf8GatherForm{fa.views, fa.first_bad, d, start, n};
 }
 static void launch_utf8_after_copy(const Utf8Launch& ul, uint32_t n, hipStream_t s)
 {
@@ -2344,62 +2202,81 @@ static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, CopyWs& c
     return hip_status(hipGetLastError());
 }
 
+// One wave per work item (unit slot, chunk) in launches of at most 2^31
+// work-items (a launch may hold at most 2^32): launch(grid, first item).
+// launch_split_grid (kmws_unmask_tile.hpp) slices blocks under a 32-bit base
+// and picks a kernel instantiation per slice: another shape, not shared.
+template <class Launch>
+static void launch_wave_slices(uint64_t items, Launch&& launch)
+{
+    constexpr uint64_t kWaves = kBlock / 64;
+    constexpr uint64_t kMaxItems = ((1ull << 32) / kBlock / 2) * kWaves;
+    for (uint64_t i0 = 0; i0 < items; i0 += kMaxItems) {
+        const uint64_t ni = items - i0 < kMaxItems ? items - i0 : kMaxItems;
+        launch(dim3((uint32_t)((ni + kWaves - 1) / kWaves)), i0);
+    }
+}
+
+static void launch_zero_words(void* p, uint64_t words, hipStream_t s)
+{
+    const uint64_t zb = (words + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((uint32_t)(zb < 1024 ? zb : 1024)), dim3(kBlock), 0, s,
+                       static_cast<uint64_t*>(p), words);
+}
+
+// An empty batch: the head cleared, start[0] = 0 and, for the validating
+// gather, the carries passed on.
+template <class Form>
+static kmws_status launch_empty(WsHead* head, uint64_t* start, hipStream_t s, const Form& form)
+{
+    if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    const kmws_status st = launch_zero(start, sizeof(uint64_t), s);
+    if constexpr (Form::kUtf8) {
+        if (st == KMWS_OK) return launch_utf8_carry_copy(form.n_streams, form.carry_in, form.carry_out, s);
+    }
+    return st;
+}
+
+// The launchers take the form as the host holds it (a form's own struct, or
+// Utf8Launch): the stages before the copy grid get plain_form(form), the copy
+// grid the form itself, for the validating gather built right before it.
+
 // The chunk form after the scan: the chunk copy grid and the dense chunks
-// (usually none: the grid of chunk_dense_kernel exits at once).  ul: the
-// validating gather (never with HEADERS), whose per-frame kernels run around
-// the copy grid.
-// okeys: the reframe's outgoing keys (RF; may be NULL).
-template <bool HEADERS, bool RF>
+// (usually none: the grid of chunk_dense_kernel exits at once).
+template <class Form>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                     const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt,
-                                     hipStream_t s, const Utf8Launch* ul, const uint32_t* okeys)
+                                     const kmws_desc* d, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
+                                     const Form& form)
 {
     const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
-    constexpr uint64_t kWaves = kBlock / 64;
-    constexpr uint64_t kMaxChunksPerLaunch = ((1ull << 32) / kBlock / 2) * kWaves;
-    const dim3 dense_grid((uint32_t)(chunks / kWaves < 512 ? chunks / kWaves + 1 : 512));
-    const Utf8Gather u = ul ? launch_utf8_before_copy(*ul, c.head, src, d, start, n, s) : Utf8Gather{};
-    for (uint64_t c0 = 0; c0 < chunks; c0 += kMaxChunksPerLaunch) {
-        const uint64_t nc = chunks - c0 < kMaxChunksPerLaunch ? chunks - c0 : kMaxChunksPerLaunch;
-        const dim3 grid((uint32_t)((nc + kWaves - 1) / kWaves));
-        if (ul)
-            hipLaunchKernelGGL(chunk_copy_utf8_kernel, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
-                               c.tiles + nt, c.head, c.dense, c0, kChunkSplit, u);
-        else if constexpr (RF)
-            hipLaunchKernelGGL(chunk_copy_reframe_kernel, grid, dim3(kBlock), 0, s, src, dst, d, flags, okeys, n, start,
-                               c.cmap, c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
-        else
-            hipLaunchKernelGGL(chunk_copy_kernel<HEADERS>, grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
-                               c.cmap, c.tiles + nt, c.head, c.dense, c0, kChunkSplit);
-    }
-    if (ul) {
-        hipLaunchKernelGGL(chunk_dense_utf8_kernel, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
-                           c.tiles + nt, c.head, c.dense, u);
-        launch_utf8_after_copy(*ul, n, s);
-    } else if constexpr (RF) {
-        hipLaunchKernelGGL(chunk_dense_reframe_kernel, dense_grid, dim3(kBlock), 0, s, src, dst, d, flags, okeys, n,
-                           start, c.cmap, c.tiles + nt, c.head, c.dense);
+    const dim3 dense_grid((uint32_t)(chunks / (kBlock / 64) < 512 ? chunks / (kBlock / 64) + 1 : 512));
+    auto copy = [&](auto dev) {
+        using Dev = decltype(dev);
+        launch_wave_slices(chunks, [&](dim3 grid, uint64_t c0) {
+            hipLaunchKernelGGL(chunk_copy_kernel<Dev>, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
+                               c.tiles + nt, c.head, c.dense, c0, kChunkSplit, dev);
+        });
+        hipLaunchKernelGGL(chunk_dense_kernel<Dev>, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
+                           c.tiles + nt, c.head, c.dense, dev);
+    };
+    if constexpr (Form::kUtf8) {
+        copy(launch_utf8_before_copy(form, c.head, src, d, start, n, s));
+        launch_utf8_after_copy(form, n, s);
     } else {
-        hipLaunchKernelGGL(chunk_dense_kernel<HEADERS>, dense_grid, dim3(kBlock), 0, s, src, dst, d, flags, n, start,
-                           c.cmap, c.tiles + nt, c.head, c.dense);
+        copy(form);
     }
     return hip_status(hipGetLastError());
 }
 
 // The chunk form behind reduce + scan (the fused unpack-gather, whose scan
 // parses the headers): chunk_map, then the copy.
-template <bool HEADERS, bool RF>
+template <class Form>
 static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                                 const uint16_t* flags, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
-                                 const Utf8Launch* ul, const uint32_t* okeys)
+                                 uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s, const Form& form)
 {
-    if constexpr (RF)
-        hipLaunchKernelGGL(chunk_map_reframe_kernel, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
-                           c.head, c.tiles, nt, c.grp, start, c.cmap);
-    else
-        hipLaunchKernelGGL(chunk_map_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, flags, n, cap,
-                           c.head, c.tiles, nt, c.grp, start, c.cmap);
-    return launch_chunk_copy<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
+    hipLaunchKernelGGL(chunk_map_kernel<Plain<Form>>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, n, cap, c.head,
+                       c.tiles, nt, c.grp, start, c.cmap, plain_form(form));
+    return launch_chunk_copy(src, dst, cap, start, d, n, c, nt, s, form);
 }
 
 // The chunk form's front in one pass: one look-back pass (chunk_scan_kernel)
@@ -2408,84 +2285,101 @@ static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap,
 // (profiles/r04aq_chunk_one_pass_ab.txt): cfg4 0.752-0.767 / 0.774-0.779
 // against 0.749-0.766 / 0.772-0.777, 1-300 B frames 0.35-0.40 / 0.45-0.49
 // against 0.34-0.39 / 0.44-0.48 (encode / gather).
-template <bool HEADERS, bool RF>
+template <class Form>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                          const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c,
-                                          hipStream_t s, const Utf8Launch* ul, const uint32_t* okeys)
+                                          const kmws_desc* d, uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
     // head | tile totals (nt + 1) | the row-prefix area, whose first nt words hold the states
-    const uint64_t words = (r16(sizeof(WsHead)) + (uint64_t)(nt + 1) * sizeof(V2) + (uint64_t)nt * 8) / 8;
-    const uint64_t zb = (words + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(zero_words_kernel, dim3((uint32_t)(zb < 1024 ? zb : 1024)), dim3(kBlock), 0, s,
-                       reinterpret_cast<uint64_t*>(c.head), words);
-    if constexpr (RF)
-        hipLaunchKernelGGL(chunk_scan_reframe_kernel, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
-                           reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
-    else
-        hipLaunchKernelGGL(chunk_scan_kernel<HEADERS>, dim3(nt), dim3(kBlock), 0, s, d, flags, n, cap, c.head,
-                           reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap);
-    return launch_chunk_copy<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
+    launch_zero_words(c.head, (r16(sizeof(WsHead)) + (uint64_t)(nt + 1) * sizeof(V2) + (uint64_t)nt * 8) / 8, s);
+    hipLaunchKernelGGL(chunk_scan_kernel<Plain<Form>>, dim3(nt), dim3(kBlock), 0, s, d, n, cap, c.head,
+                       reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap, plain_form(form));
+    return launch_chunk_copy(src, dst, cap, start, d, n, c, nt, s, form);
 }
 
 // The copy form after the scan: chunks (small mean) or the prologue and the
 // unit copy grid.
-template <bool HEADERS, bool RF = false>
+template <class Form>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                    const kmws_desc* d, const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                                    const Utf8Launch* ul = nullptr, const uint32_t* okeys = nullptr)
+                                    const kmws_desc* d, uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
 {
     const uint32_t nt = (uint32_t)n_tiles(n);
-    if (use_chunks(n, cap)) return launch_chunks<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, nt, s, ul, okeys);
-    if constexpr (RF)
-        hipLaunchKernelGGL(prologue_reframe_kernel, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, okeys,
-                           n, cap, c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
-    else
-        hipLaunchKernelGGL(prologue_kernel<HEADERS>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, flags, n,
-                           cap, c.head, c.tiles, nt, c.grp, start, c.rec, c.edge);
+    if (use_chunks(n, cap)) return launch_chunks(src, dst, cap, start, d, n, c, nt, s, form);
+    hipLaunchKernelGGL(prologue_kernel<Plain<Form>>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, n, cap,
+                       c.head, c.tiles, nt, c.grp, start, c.rec, c.edge, plain_form(form));
     // Occupancy: runs of large frames stream faster with 5 blocks per CU (fewer
     // concurrent DRAM streams; capped by 32 KiB of dynamic LDS per block),
     // batches of small frames need every wave slot to hide their per-unit
     // latency.  cap / n bounds the mean region size from above.
     const unsigned lds_pad = cap / n >= 16384 ? 32768u : 0u;
-    const uint64_t units = max_units(n, cap);  // upper bound; surplus waves exit at once
-    constexpr uint64_t kWavesPerBlock = kBlock / 64;
-    constexpr uint64_t kMaxUnitsPerLaunch = ((1ull << 32) / kBlock / 2) * kWavesPerBlock;
-    const Utf8Gather u = ul ? launch_utf8_before_copy(*ul, c.head, src, d, start, n, s) : Utf8Gather{};
-    for (uint64_t u0 = 0; u0 < units; u0 += kMaxUnitsPerLaunch) {
-        const uint64_t nu = units - u0 < kMaxUnitsPerLaunch ? units - u0 : kMaxUnitsPerLaunch;
-        const dim3 grid((uint32_t)((nu + kWavesPerBlock - 1) / kWavesPerBlock));
-        if (ul)
-            hipLaunchKernelGGL(copy_utf8_kernel, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec, c.edge,
-                               c.head, u0, kCopySplit, u);
-        else
-            hipLaunchKernelGGL(copy_kernel<HEADERS>, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt, c.rec,
-                               c.edge, c.head, u0, kCopySplit);
+    // upper bound on the units; surplus waves exit at once.  The records and
+    // edge words hold the rest of the form: copy_kernel takes its UTF-8 part only.
+    auto copy = [&](auto dev) {
+        launch_wave_slices(max_units(n, cap), [&](dim3 grid, uint64_t u0) {
+            hipLaunchKernelGGL(copy_kernel<decltype(dev)>, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt,
+                               c.rec, c.edge, c.head, u0, kCopySplit, dev);
+        });
+    };
+    if constexpr (Form::kUtf8) {
+        copy(launch_utf8_before_copy(form, c.head, src, d, start, n, s));
+        launch_utf8_after_copy(form, n, s);
+    } else {
+        copy(GatherForm{});
     }
-    if (ul) launch_utf8_after_copy(*ul, n, s);
     return hip_status(hipGetLastError());
 }
 
 // Encode / gather: reduce (row and tile totals), scan the tile totals, the
 // prologue (offsets, edge words, unit records), the copy grid.  Four launches,
 // stream-ordered, nothing on the host in between.
-template <bool HEADERS, bool RF = false>
+template <class Form>
 static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                               const uint16_t* flags, uint32_t n, CopyWs& c, hipStream_t s,
-                               const Utf8Launch* ul = nullptr, const uint32_t* okeys = nullptr)
+                               uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
 {
-    if (n == 0) {
-        if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-        return launch_zero(start, sizeof(uint64_t), s);
-    }
-    if (use_chunks(n, cap))
-        return launch_chunks_one_pass<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, s, ul, okeys);
-    const kmws_status st = RF        ? launch_reduce(ReframeSize{d, flags}, n, start, c, s)
-                           : HEADERS ? launch_reduce(WireSize{d, flags}, n, start, c, s)
-                                     : launch_reduce(PayloadSize{d}, n, start, c, s);
+    if (n == 0) return launch_empty(c.head, start, s, form);
+    if (use_chunks(n, cap)) return launch_chunks_one_pass(src, dst, cap, start, d, n, c, s, form);
+    const kmws_status st = launch_reduce(DescSize<Plain<Form>>{d, plain_form(form)}, n, start, c, s);
     if (st != KMWS_OK) return st;
-    return launch_copy_tail<HEADERS, RF>(src, dst, cap, start, d, flags, n, c, s, ul, okeys);
+    return launch_copy_tail(src, dst, cap, start, d, n, c, s, form);
 }
+
+// What lies behind the copy's workspace (NULL without one).
+static char* behind_copy_ws(void* workspace, uint32_t n, uint64_t dst_cap)
+{
+    return workspace ? static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)) : nullptr;
+}
+
+static bool have_device()
+{
+    static const bool have = kmws_device_count() > 0;
+    return have;
+}
+
+// The argument checks of the seven copy entries, and the workspace carved.
+// args_ok: the entry's own pointers and values.  Encode, gather and reframe:
+// whatever fails, BUFFER_TOO_SMALL if a workspace is there and too small for
+// the form, else INVALID_PARAM; the reframe then needs a device.  The
+// validating gather: its pointers, then utf8_stream_args_check's order.
+template <class Form>
+static kmws_status copy_args_check(bool args_ok, const void* src, const void* dst, uint32_t n, uint64_t dst_cap,
+                                   void* workspace, size_t workspace_bytes, CopyWs& c, const Form& form)
+{
+    if constexpr (Form::kUtf8) {
+        if (!args_ok) return KMWS_ERR_INVALID_PARAM;
+        const kmws_status st =
+            utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams,
+                                   kmws_gather_utf8_workspace_size(n, dst_cap, form.n_streams), workspace_bytes);
+        if (st != KMWS_OK) return st;
+        return carve(workspace, workspace_bytes, n, dst_cap, c) ? KMWS_OK : KMWS_ERR_INVALID_PARAM;
+    } else {
+        const size_t need = Form::kReframe ? kmws_reframe_workspace_size(n, dst_cap) : copy_ws_size(n, dst_cap);
+        if (!args_ok || (reinterpret_cast<uintptr_t>(dst) & 15u) || (reinterpret_cast<uintptr_t>(src) & 15u) ||
+            !workspace || workspace_bytes < need || !carve(workspace, workspace_bytes, n, dst_cap, c))
+            return workspace && workspace_bytes < need ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_ERR_INVALID_PARAM;
+        return !Form::kReframe || have_device() ? KMWS_OK : KMWS_ERR_NOT_SUPPORTED;
+    }
+}
+static bool mode_ok(int mode) { return mode == KMWS_MODE_CLIENT || mode == KMWS_MODE_SERVER; }
 
 }  // namespace kmws
 
@@ -2495,18 +2389,28 @@ extern "C" {
 
 size_t kmws_copy_workspace_size(uint32_t n, uint64_t dst_cap) { return copy_ws_size(n, dst_cap); }
 
+// The copy's workspace, then the outgoing flags kmws_unpack_reframe derives (2 B per frame).
+size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap)
+{
+    return r256(copy_ws_size(n, dst_cap)) + r16(2ull * n);
+}
+// The copy's workspace, then the validator's per-frame and per-stream arrays.
+size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
+{
+    return r256(copy_ws_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
+}
 kmws_status kmws_encode_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,
                               uint8_t* dst, uint64_t dst_cap, uint64_t* wire_off, void* workspace,
                               size_t workspace_bytes, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     CopyWs c;
-    if (!wire_off || (n && (!src || !descs || !flags || !dst)) || (reinterpret_cast<uintptr_t>(dst) & 15u) ||
-        (reinterpret_cast<uintptr_t>(src) & 15u) || !carve(workspace, workspace_bytes, n, dst_cap, c))
-        return workspace && workspace_bytes < copy_ws_size(n, dst_cap) ? KMWS_ERR_BUFFER_TOO_SMALL
-                                                                       : KMWS_ERR_INVALID_PARAM;
+    const EncodeForm form{flags};
+    const kmws_status ck = copy_args_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
+                                           workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
     kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy<true>(src, dst, dst_cap, wire_off, descs, flags, n, c, s);
+    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
 }
 
 kmws_status kmws_gather_unmask(const uint8_t* src, const kmws_desc* descs, uint32_t n, uint8_t* dst,
@@ -2515,12 +2419,11 @@ kmws_status kmws_gather_unmask(const uint8_t* src, const kmws_desc* descs, uint3
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     CopyWs c;
-    if (!dst_off || (n && (!src || !descs || !dst)) || (reinterpret_cast<uintptr_t>(dst) & 15u) ||
-        (reinterpret_cast<uintptr_t>(src) & 15u) || !carve(workspace, workspace_bytes, n, dst_cap, c))
-        return workspace && workspace_bytes < copy_ws_size(n, dst_cap) ? KMWS_ERR_BUFFER_TOO_SMALL
-                                                                       : KMWS_ERR_INVALID_PARAM;
+    const kmws_status ck = copy_args_check(dst_off && (!n || (src && descs && dst)), src, dst, n, dst_cap, workspace,
+                                           workspace_bytes, c, GatherForm{});
+    if (ck != KMWS_OK) return ck;
     kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy<false>(src, dst, dst_cap, dst_off, descs, nullptr, n, c, s);
+    return launch_copy(src, dst, dst_cap, dst_off, descs, n, c, s, GatherForm{});
 }
 
 // Header parse fused into the gather: status cleared, reduce over the parsed
@@ -2533,56 +2436,32 @@ kmws_status kmws_unpack_gather(const uint8_t* wire, uint64_t wire_len, const uin
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     CopyWs c;
-    if (!dst_off || (n && (!wire || !hdr_off || !out_desc || !dst)) || (reinterpret_cast<uintptr_t>(dst) & 15u) ||
-        (reinterpret_cast<uintptr_t>(wire) & 15u) || (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) ||
-        !carve(workspace, workspace_bytes, n, dst_cap, c))
-        return workspace && workspace_bytes < copy_ws_size(n, dst_cap) ? KMWS_ERR_BUFFER_TOO_SMALL
-                                                                       : KMWS_ERR_INVALID_PARAM;
+    const kmws_status ck = copy_args_check(dst_off && (!n || (wire && hdr_off && out_desc && dst)) && mode_ok(mode),
+                                           wire, dst, n, dst_cap, workspace, workspace_bytes, c, GatherForm{});
+    if (ck != KMWS_OK) return ck;
+    if (n == 0) return launch_empty(c.head, dst_off, s, GatherForm{});
     if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    if (n == 0) return launch_zero(dst_off, sizeof(uint64_t), s);
     kmws::note_device_batch(wire_len + dst_cap, s);
-    kmws_status st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
-                                                     c.head},
-                                   n, dst_off, c, s);
+    const kmws_status st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags,
+                                                           out_err, c.head},
+                                         n, dst_off, c, s);
     if (st != KMWS_OK) return st;
-    return launch_copy_tail<false>(wire, dst, dst_cap, dst_off, out_desc, nullptr, n, c, s);
+    return launch_copy_tail(wire, dst, dst_cap, dst_off, out_desc, n, c, s, GatherForm{});
 }
 
 // ---- unmask and re-encode in one pass over the payload ----
-// The copy's workspace, then the outgoing flags kmws_unpack_reframe derives (2 B per frame).
-size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap)
-{
-    return r256(copy_ws_size(n, dst_cap)) + r16(2ull * n);
-}
-
-static bool have_device()
-{
-    static const bool have = kmws_device_count() > 0;
-    return have;
-}
-
-// kmws_encode_batch's checks and return values on the reframe's workspace size.
-static kmws_status reframe_check(bool ptrs_ok, const void* src, const void* dst, uint32_t n, uint64_t dst_cap,
-                                 void* workspace, size_t workspace_bytes, CopyWs& c)
-{
-    const size_t need = kmws_reframe_workspace_size(n, dst_cap);
-    if (!ptrs_ok || (reinterpret_cast<uintptr_t>(dst) & 15u) || (reinterpret_cast<uintptr_t>(src) & 15u) ||
-        !workspace || workspace_bytes < need || !carve(workspace, workspace_bytes, n, dst_cap, c))
-        return workspace && workspace_bytes < need ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_ERR_INVALID_PARAM;
-    return have_device() ? KMWS_OK : KMWS_ERR_NOT_SUPPORTED;
-}
-
 kmws_status kmws_reframe_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
                                const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
                                uint64_t* wire_off, void* workspace, size_t workspace_bytes, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     CopyWs c;
-    const kmws_status st = reframe_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
-                                         workspace, workspace_bytes, c);
-    if (st != KMWS_OK) return st;
+    const ReframeForm form{flags, out_keys};
+    const kmws_status ck = copy_args_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
+                                           workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
     if (n) kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy<true, true>(src, dst, dst_cap, wire_off, descs, flags, n, c, s, nullptr, out_keys);
+    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
 }
 
 // The parse fused into the reframe's scan: status cleared, reduce over the
@@ -2596,61 +2475,39 @@ kmws_status kmws_unpack_reframe(const uint8_t* wire, uint64_t wire_len, const ui
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     CopyWs c;
-    if ((mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) || relay_opcodes > 0xFFFFu ||
-        (out_mask != 0 && out_mask != 1))
-        return KMWS_ERR_INVALID_PARAM;
-    const kmws_status ck = reframe_check(wire_off && (!n || (wire && hdr_off && out_desc && dst)), wire, dst, n,
-                                         dst_cap, workspace, workspace_bytes, c);
+    if (!mode_ok(mode) || relay_opcodes > 0xFFFFu || (out_mask != 0 && out_mask != 1)) return KMWS_ERR_INVALID_PARAM;
+    uint16_t* oflags = reinterpret_cast<uint16_t*>(behind_copy_ws(workspace, n, dst_cap));
+    const ReframeForm form{oflags, out_keys};
+    const kmws_status ck = copy_args_check(wire_off && (!n || (wire && hdr_off && out_desc && dst)), wire, dst, n,
+                                           dst_cap, workspace, workspace_bytes, c, form);
     if (ck != KMWS_OK) return ck;
+    if (n == 0) return launch_empty(c.head, wire_off, s, form);
     if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    if (n == 0) return launch_zero(wire_off, sizeof(uint64_t), s);
     kmws::note_device_batch(wire_len + dst_cap, s);
-    uint16_t* oflags = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)));
     const HeaderReframeSize size{HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
                                                    c.head},
                                  oflags, relay_opcodes, (uint32_t)out_mask};
     const kmws_status st = launch_reduce(size, n, wire_off, c, s);
     if (st != KMWS_OK) return st;
-    return launch_copy_tail<true, true>(wire, dst, dst_cap, wire_off, out_desc, oflags, n, c, s, nullptr, out_keys);
+    return launch_copy_tail(wire, dst, dst_cap, wire_off, out_desc, n, c, s, form);
 }
 
 // ---- gather, unmask and UTF-8 check in one pass over the payload ----
-// The copy's workspace, then the validator's per-frame and per-stream arrays.
-size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
-{
-    return r256(copy_ws_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
-}
-
-// The checks both entries share: the gather's pointers whatever n is, then the
-// stream arguments and the workspace (utf8_stream_args_check).
-static kmws_status gather_utf8_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, uint64_t dst_cap,
-                                     const uint32_t* stream_first, uint32_t n_streams, size_t workspace_bytes)
-{
-    if (!ptrs_ok) return KMWS_ERR_INVALID_PARAM;
-    return utf8_stream_args_check(true, a, b, n, stream_first, n_streams,
-                                  kmws_gather_utf8_workspace_size(n, dst_cap, n_streams), workspace_bytes);
-}
-
 kmws_status kmws_gather_unmask_utf8(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,
                                     uint8_t* dst, uint64_t dst_cap, uint64_t* dst_off, const uint32_t* stream_first,
                                     uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool ptrs = dst_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
-    kmws_status st = gather_utf8_check(ptrs, src, dst, n, dst_cap, stream_first, n_streams, workspace_bytes);
-    if (st != KMWS_OK) return st;
     CopyWs c;
-    if (!carve(workspace, workspace_bytes, n, dst_cap, c)) return KMWS_ERR_INVALID_PARAM;
-    if (n == 0) {
-        st = launch_copy<false>(src, dst, dst_cap, dst_off, descs, nullptr, 0, c, s);
-        return st != KMWS_OK ? st : launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
-    }
     // the plain gather has no source span: one the descriptor check never trips on
-    const Utf8Launch ul{static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)), flags, ~0ull, stream_first,
-                        n_streams, carry_in, carry_out, out_utf8};
-    kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy<false>(src, dst, dst_cap, dst_off, descs, nullptr, n, c, s, &ul);
+    const Utf8Launch form{behind_copy_ws(workspace, n, dst_cap), flags, ~0ull, stream_first, n_streams, carry_in,
+                          carry_out, out_utf8};
+    const bool ptrs = dst_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
+    const kmws_status ck = copy_args_check(ptrs, src, dst, n, dst_cap, workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
+    if (n) kmws::note_device_batch(2 * dst_cap, s);
+    return launch_copy(src, dst, dst_cap, dst_off, descs, n, c, s, form);
 }
 
 kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
@@ -2660,24 +2517,21 @@ kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, cons
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) return KMWS_ERR_INVALID_PARAM;
-    const bool ptrs = dst_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
-    kmws_status st = gather_utf8_check(ptrs, wire, dst, n, dst_cap, stream_first, n_streams, workspace_bytes);
-    if (st != KMWS_OK) return st;
     CopyWs c;
-    if (!carve(workspace, workspace_bytes, n, dst_cap, c)) return KMWS_ERR_INVALID_PARAM;
+    if (!mode_ok(mode)) return KMWS_ERR_INVALID_PARAM;
+    const Utf8Launch form{behind_copy_ws(workspace, n, dst_cap), out_flags, wire_len, stream_first, n_streams, carry_in,
+                          carry_out, out_utf8};
+    const bool ptrs = dst_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
+    const kmws_status ck = copy_args_check(ptrs, wire, dst, n, dst_cap, workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
+    if (n == 0) return launch_empty(c.head, dst_off, s, form);
     if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    if (n == 0) {
-        st = launch_zero(dst_off, sizeof(uint64_t), s);
-        return st != KMWS_OK ? st : launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
-    }
     kmws::note_device_batch(wire_len + dst_cap, s);
-    st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err, c.head}, n,
-                       dst_off, c, s);
+    const kmws_status st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags,
+                                                           out_err, c.head},
+                                         n, dst_off, c, s);
     if (st != KMWS_OK) return st;
-    const Utf8Launch ul{static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)), out_flags, wire_len,
-                        stream_first, n_streams, carry_in, carry_out, out_utf8};
-    return launch_copy_tail<false>(wire, dst, dst_cap, dst_off, out_desc, nullptr, n, c, s, &ul);
+    return launch_copy_tail(wire, dst, dst_cap, dst_off, out_desc, n, c, s, form);
 }
 
 // head, then one 64-bit state per 2048-frame tile (pack_headers_chain_kernel)
@@ -2696,15 +2550,9 @@ kmws_status kmws_pack_headers(const kmws_desc* descs, const uint16_t* flags, uin
         if (workspace_bytes < kmws_pack_headers_workspace_size(n)) return KMWS_ERR_BUFFER_TOO_SMALL;
         WsHead* head = static_cast<WsHead*>(workspace);
         uint64_t* st = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + r16(sizeof(WsHead)));
-        if (n == 0) {
-            if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-            return launch_zero(wire_off, sizeof(uint64_t), s);
-        }
+        if (n == 0) return launch_empty(head, wire_off, s, EncodeForm{flags});
         // two launches: zero the head and the tile states, then the one-pass kernel
-        const uint64_t words = kmws_pack_headers_workspace_size(n) / 8;
-        const uint64_t zb = (words + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(zero_words_kernel, dim3((uint32_t)(zb < 1024 ? zb : 1024)), dim3(kBlock), 0, s,
-                           reinterpret_cast<uint64_t*>(head), words);
+        launch_zero_words(head, kmws_pack_headers_workspace_size(n) / 8, s);
         hipLaunchKernelGGL(pack_headers_chain_kernel, dim3((uint32_t)n_tiles(n)), dim3(kBlock), 0, s, descs, flags, n, h,
                            hl_out, wire_off, st, head);
         return hip_status(hipGetLastError());

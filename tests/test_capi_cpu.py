@@ -193,6 +193,108 @@ def test_batch_entries_reject_bad_arguments_before_any_device_work():
     assert L.kmws_find_headers_streams(None, 0, None, 0, None, 0, None, None, None) == 0  # nothing to do
 
 
+def _copy_entry_rows():
+    """(entry, argument list, expected status) for the five copy entries the
+    reframe's table (test_reframe_capi_cpu.py) does not cover.  Pointers are
+    fakes that are never dereferenced: every row fails its checks."""
+    import ctypes as C
+    L = kmws.lib()
+    n, cap, S = 5, 1 << 16, kmws.SERVER
+    fake, odd = C.c_void_p(4096), C.c_void_p(4096 + 8)
+    bad, small = kmws.ERR_INVALID_PARAM, kmws.ERR_BUFFER_TOO_SMALL
+    need = L.kmws_copy_workspace_size(n, cap)
+    need8 = L.kmws_gather_utf8_workspace_size(n, cap, 1)
+    need0 = L.kmws_gather_utf8_workspace_size(0, cap, 1)
+    # name: (valid call, index of n, of workspace and of workspace_bytes, required pointers, aligned pointers,
+    #        index of mode or None, sufficient size)
+    entries = {
+        #                     src   descs flags n  dst   cap  off   ws    bytes stream
+        "kmws_encode_batch": ([fake, fake, fake, n, fake, cap, fake, fake, need, None],
+                              3, 7, 8, (0, 1, 2, 4, 6, 7), (0, 4), None),
+        #                      src   descs n  dst   cap  off   ws    bytes stream
+        "kmws_gather_unmask": ([fake, fake, n, fake, cap, fake, fake, need, None],
+                               2, 6, 7, (0, 1, 3, 5, 6), (0, 3), None),
+        #                      wire  len      hdr   n  mode desc  flags err   dst   cap  off   ws    bytes stream
+        "kmws_unpack_gather": ([fake, 1 << 16, fake, n, S, fake, fake, fake, fake, cap, fake, fake, need, None],
+                               3, 11, 12, (0, 2, 5, 8, 10, 11), (0, 8), 4),
+        #                           src   descs flags n  dst   cap  off   first ns carry      utf8  ws    bytes stream
+        "kmws_gather_unmask_utf8": ([fake, fake, fake, n, fake, cap, fake, None, 1, None, None, fake, fake, need8, None],
+                                    3, 12, 13, (0, 1, 2, 4, 6, 11, 12), (0, 4), None),
+        #                           wire  len      hdr   n  mode desc  flags err   dst   cap  off   first ns carry
+        "kmws_unpack_gather_utf8": ([fake, 1 << 16, fake, n, S, fake, fake, fake, fake, cap, fake, None, 1, None, None,
+                                     fake, fake, need8, None],  # out_utf8, workspace, bytes, stream
+                                    3, 16, 17, (0, 2, 5, 6, 8, 10, 15, 16), (0, 8), 4),
+    }
+    rows = []
+
+    def row(name, ok, want, **changes):
+        args = list(ok)
+        for i, v in changes.items():
+            args[int(i[1:])] = v
+        rows.append((name, args, want))
+
+    for name, (ok, i_n, i_ws, i_sz, required, aligned, i_mode) in entries.items():
+        plain = not name.endswith("_utf8")
+        full = ok[i_sz]
+        for i in required:  # each required pointer NULL in turn (the workspace among them: NULL, sufficient size)
+            row(name, ok, bad, **{f"a{i}": None})
+        for i in aligned:  # 16-byte alignment of the source and of dst
+            row(name, ok, bad, **{f"a{i}": odd})
+        row(name, ok, small, **{f"a{i_sz}": full - 1})
+        row(name, ok, small, **{f"a{i_sz}": 0})
+        # a NULL workspace is a bad argument whatever size goes with it
+        row(name, ok, bad, **{f"a{i_ws}": None, f"a{i_sz}": full - 1})
+        if i_mode is not None:
+            for m in (7, -1):
+                row(name, ok, bad, **{f"a{i_mode}": m})
+        if plain:
+            # with a workspace that is there and too small, that is what any failing call reports
+            row(name, ok, small, a0=None, **{f"a{i_sz}": full - 1})
+            row(name, ok, small, a0=odd, **{f"a{i_sz}": full - 1})
+            if i_mode is not None:
+                row(name, ok, small, **{f"a{i_mode}": 7, f"a{i_sz}": full - 1})
+        else:
+            # utf8_stream_args_check's order: counts, pointers, alignment, streams, then the size
+            row(name, ok, bad, a0=None, **{f"a{i_sz}": full - 1})
+            row(name, ok, bad, a0=odd, **{f"a{i_sz}": full - 1})
+            row(name, ok, bad, **{f"a{i_n}": 1 << 31})
+            i_first = i_ws - 5  # stream_first, then n_streams
+            row(name, ok, bad, **{f"a{i_first + 1}": 0})
+            row(name, ok, bad, **{f"a{i_first + 1}": 2})  # several streams need stream_first
+            row(name, ok, bad, **{f"a{i_first + 1}": 1 << 31, f"a{i_first}": fake})
+            row(name, ok, bad, **{f"a{i_first + 1}": 0, f"a{i_sz}": 0})
+            if i_mode is not None:  # the mode comes before everything else
+                row(name, ok, bad, **{f"a{i_mode}": 7, f"a{i_sz}": 0})
+        # an empty batch with NULL data pointers still needs its offsets array and its workspace
+        empty = [None if isinstance(v, C.c_void_p) else v for v in ok]
+        empty[i_n] = 0
+        i_off = i_ws - 1 if plain else i_ws - 6
+        size0 = L.kmws_copy_workspace_size(0, cap) if plain else need0
+        row(name, empty, bad, **{f"a{i_ws}": fake, f"a{i_sz}": size0})               # offsets NULL
+        row(name, empty, bad, **{f"a{i_off}": fake, f"a{i_sz}": size0})              # workspace NULL
+        row(name, empty, small, **{f"a{i_off}": fake, f"a{i_ws}": fake, f"a{i_sz}": size0 - 1})
+        if plain:
+            row(name, empty, bad, **{f"a{i_off}": fake, f"a{i_sz}": size0 - 1})      # NULL and short: still a bad argument
+        else:
+            row(name, empty, bad, a0=odd, **{f"a{i_off}": fake, f"a{i_ws}": fake, f"a{i_sz}": size0})
+    return rows
+
+
+def test_copy_entries_reject_bad_arguments_before_any_device_work():
+    """The status every copy entry returns for each bad argument, and which check
+    wins when two fail: kmws_encode_batch, kmws_gather_unmask and
+    kmws_unpack_gather report BUFFER_TOO_SMALL only for a workspace that is there
+    and too small (then whatever else is wrong), otherwise INVALID_PARAM; the
+    UTF-8 gathers check their mode, then follow kmws_utf8_validate's order, the
+    size last.  No row reaches a launch, so the table holds with and without a
+    device."""
+    L = kmws.lib()
+    rows = _copy_entry_rows()
+    assert len(rows) >= 100 and len({r[0] for r in rows}) == 5
+    got = [(name, i, getattr(L, name)(*args)) for i, (name, args, _) in enumerate(rows)]
+    assert got == [(name, i, want) for i, (name, _, want) in enumerate(rows)]
+
+
 def test_copy_workspace_size_follows_the_copy_form():
     """kmws_copy_workspace_size (no device needed): below a 16 KiB mean region
     bound (dst_cap / n) the chunk form's 8 B per 4 KiB output chunk, from it the
