@@ -86,7 +86,7 @@ struct kmws_decoder {
     // synchronous-feed delivery lists (the staging is borrowed per call: StagePool)
     std::vector<Pending> pending;
     std::vector<std::vector<uint8_t>> held;
-    std::vector<kmws_desc> chunk_descs;
+    ExtraBuf chunk;  // the caller's chunk when it is pinned: payloads unmasked where they lie
     // kmws_decoder_set_utf8_check.  The stream's message state, both halves
     // (kmws_utf8_stream.hpp): the parse-time half advances in the feeds' sinks,
     // the delivery-time half (which message was reported BAD) when verdicts are
@@ -95,16 +95,30 @@ struct kmws_decoder {
     // and only for items that are still live.
     bool utf8_check = false;
     Utf8Stream utf8;
-    std::vector<Utf8View> chunk_views;  // one per chunk_descs entry while the check is on
 
-    // Parse-time half for a completed frame whose payload lies contiguous (and
-    // still masked) at `payload`.
-    Utf8StreamView utf8_parse(const kmws_frame_hdr& h, const uint8_t* payload, uint32_t key)
+    // What both feeds derive from a completed frame whose payload lies
+    // contiguous (and still masked) at `payload`.
+    struct Facts {
+        bool masked;   // has payload to unmask: handleDataMask is a no-op otherwise (:293, :305)
+        bool checked;  // has payload for the UTF-8 check (an empty frame needs no device work: rule (b) is decided here)
+        uint32_t key;
+        uint32_t dkey;      // its descriptor's key; 0 when unmasked: checked, not stored
+        Utf8StreamView uv;  // the frame's view from the parse-time half, which advances here (w == 0: not checked)
+        bool gpu() const { return masked || checked; }
+    };
+    Facts frame_facts(const kmws_frame_hdr& h, const uint8_t* payload)
     {
-        if (!utf8_check) return Utf8StreamView{};
-        uint32_t nb = 0;
-        const uint32_t tail = utf8_stream_tail(payload, h.length, h.mask ? key : 0u, &nb);
-        return utf8_stream_frame(utf8, op_byte_of(h), tail, nb);
+        Facts f{};
+        f.masked = h.mask && h.length;
+        std::memcpy(&f.key, h.maskey, 4);
+        f.dkey = f.masked ? f.key : 0u;
+        if (utf8_check) {
+            uint32_t nb = 0;
+            const uint32_t tail = utf8_stream_tail(payload, h.length, h.mask ? f.key : 0u, &nb);
+            f.uv = utf8_stream_frame(utf8, op_byte_of(h), tail, nb);
+        }
+        f.checked = (f.uv.w & kUtf8Checked) != 0u && h.length;
+        return f;
     }
 
     void reset_ctx()  // DecodeContext::reset, WSHandler.h:66-72 (capacity kept)
@@ -120,50 +134,23 @@ struct kmws_decoder {
 // flight each; more are made if needed).
 constexpr int kWarmStages = 4;
 
-struct kmws_rx_batch {
+namespace {
+
+// The generations of an rx or a tx batch: the pinned stage being fed, those of
+// the submitted generations with their launches in flight (submit order), the
+// finished ones kept for reuse, the stream they all share and the caller's
+// attached ring.  Gen: what the batch keeps of a submitted generation beside
+// its `stage` member.
+template <class Gen>
+struct GenQueue {
     BatchStream bstream;  // first: destroyed after every stage that uses it
-    struct Item {
-        // Identity, and with the UTF-8 check the home of the connection's
-        // delivery-time state (Utf8Stream::bad_msg / dropped_msg).  A callback
-        // may destroy a decoder, so it is dereferenced in one place only:
-        // rx_verdicts / rx_drop_utf8, which run when no callback of the
-        // generation has run yet (or none ever will) and touch only items
-        // that are still `live` and checked.  That is safe because a decoder may
-        // be destroyed only after its frames were delivered or after
-        // kmws_rx_batch_discard (the "destroyed" return discards too), and both
-        // clear `live` on every item of it -- in the generation being fed, in
-        // every generation in flight and in the one being delivered -- before
-        // the decoder can be gone.  After kmws_rx_batch_discard the decoder's
-        // state is therefore never read or written again through the batch.
-        kmws_decoder* dec;
-        kmws_frame_cb cb;
-        void* user;
-        kmws_frame_hdr hdr;
-        size_t off;       // payload offset in the generation's staging area (direct == nullptr)
-        uint8_t* direct;  // payload in the attached ring (no copy)
-        bool live;        // false once discarded
-        Utf8StreamView uv;  // the frame's view from the parse-time half (w == 0: not checked)
-        uint32_t slot;      // its verdict byte in the generation's stage (kNoSlot: none)
-    };
-    // One submitted generation: its frames, and the pinned stage that holds
-    // their staged payloads and the unmask launch in flight.
-    struct Gen {
-        std::unique_ptr<PinnedStage> stage;
-        std::vector<Item> items;
-    };
     std::unique_ptr<PinnedStage> stage;  // the generation being fed
-    std::vector<Item> items;
-    uint64_t pending_bytes = 0;  // masked payload bytes of `items`
-    std::vector<kmws_desc> ring_descs;
-    std::vector<Utf8View> ring_views;    // empty: no ring descriptor is checked; else one per descriptor so far
-    std::deque<Gen> inflight;            // submitted, not yet delivered (submit order)
+    std::deque<Gen> inflight;
     std::vector<std::unique_ptr<PinnedStage>> spare;
-    std::vector<Item>* delivering = nullptr;  // the generation whose callbacks are running
-    uint8_t* ring = nullptr;  // caller's pinned receive ring (optional)
-    uint8_t* ring_dv = nullptr;  // its device view, looked up once at attach
-    size_t ring_bytes = 0;
+    // The caller's pinned ring (optional), its device view looked up once at
+    // attach, and the descriptors of the generation being fed that lie in it.
+    ExtraBuf ring;
     int device = 0;
-    bool flushing = false;  // feeding / submitting / polling from inside a delivery is refused
 
     std::unique_ptr<PinnedStage> take_stage()
     {
@@ -176,7 +163,7 @@ struct kmws_rx_batch {
         if (s && s->init(device, bstream.s) != KMWS_OK) s.reset();
         return s;
     }
-    // the stream and a few warm stages, made before the first loop iteration
+    // the stream, a few warm stages and the first generation's, made before the first loop iteration
     kmws_status prepare(int dev)
     {
         device = dev;
@@ -187,8 +174,112 @@ struct kmws_rx_batch {
             st = s->warm();
             spare.push_back(std::move(s));
         }
+        if (st == KMWS_OK && !(stage = take_stage())) st = KMWS_ERR_FAILED;
         return st;
     }
+    // p == nullptr detaches; a ring must be pinned (one of no bytes has no device view)
+    kmws_status attach(uint8_t* p, size_t bytes)
+    {
+        uint8_t* dv = p && bytes ? static_cast<uint8_t*>(device_view(p)) : nullptr;
+        if (p && !dv) return KMWS_ERR_INVALID_PARAM;
+        ring.base = p;
+        ring.dv = dv;
+        ring.span = p ? bytes : 0;
+        return KMWS_OK;
+    }
+    // Submitting takes the successor stage first (take_stage(): without one the
+    // generation stays as it is), then launches -- a flush (sync) runs one
+    // synchronous job on the device's resident worker when it fits one, else
+    // launches and waits -- and then either rotates or restores.
+    kmws_status launch(bool sync)
+    {
+        const kmws_status st = sync ? stage->run(ring) : stage->launch(ring, kResMaxBytesAsync);
+        ring.list.clear();
+        return st;
+    }
+    // launched: the stage leaves with g, next takes its place
+    Gen& rotate(Gen g, std::unique_ptr<PinnedStage> next)
+    {
+        g.stage = std::move(stage);
+        inflight.push_back(std::move(g));
+        stage = std::move(next);
+        return inflight.back();
+    }
+    // not launched: the stage stays, emptied
+    void restore(std::unique_ptr<PinnedStage> next)
+    {
+        stage->clear();
+        spare.push_back(std::move(next));
+    }
+    // a finished generation's stage
+    void retire(std::unique_ptr<PinnedStage> s)
+    {
+        s->clear();
+        spare.push_back(std::move(s));
+    }
+    // before the batch is destroyed: no launch may outlive its pinned memory
+    void drain()
+    {
+        for (Gen& g : inflight) (void)g.stage->wait();
+    }
+};
+
+template <class Batch>
+Batch* batch_create(int device)
+{
+    Batch* b = new (std::nothrow) Batch();
+    if (b && b->prepare(resolve_device(device)) != KMWS_OK) {
+        delete b;
+        b = nullptr;
+    }
+    return b;
+}
+
+template <class Batch>
+void batch_destroy(Batch* b)
+{
+    if (!b) return;
+    b->drain();
+    delete b;
+}
+
+struct RxItem {
+    // Identity, and with the UTF-8 check the home of the connection's
+    // delivery-time state (Utf8Stream::bad_msg / dropped_msg).  A callback
+    // may destroy a decoder, so it is dereferenced in one place only:
+    // rx_verdicts / rx_drop_utf8, which run when no callback of the
+    // generation has run yet (or none ever will) and touch only items
+    // that are still `live` and checked.  That is safe because a decoder may
+    // be destroyed only after its frames were delivered or after
+    // kmws_rx_batch_discard (the "destroyed" return discards too), and both
+    // clear `live` on every item of it -- in the generation being fed, in
+    // every generation in flight and in the one being delivered -- before
+    // the decoder can be gone.  After kmws_rx_batch_discard the decoder's
+    // state is therefore never read or written again through the batch.
+    kmws_decoder* dec;
+    kmws_frame_cb cb;
+    void* user;
+    kmws_frame_hdr hdr;
+    size_t off;       // payload offset in the generation's staging area (direct == nullptr)
+    uint8_t* direct;  // payload in the attached ring (no copy)
+    bool live;        // false once discarded
+    Utf8StreamView uv;  // the frame's view from the parse-time half (w == 0: not checked)
+    uint32_t slot;      // its verdict byte in the generation's stage (kNoSlot: none)
+};
+// One submitted generation: its frames, and the pinned stage that holds
+// their staged payloads and the unmask launch in flight.
+struct RxGen {
+    std::unique_ptr<PinnedStage> stage;
+    std::vector<RxItem> items;
+};
+
+}  // namespace
+
+struct kmws_rx_batch : GenQueue<RxGen> {
+    std::vector<RxItem> items;   // of the generation being fed
+    uint64_t pending_bytes = 0;  // masked payload bytes of `items`
+    std::vector<RxItem>* delivering = nullptr;  // the generation whose callbacks are running
+    bool flushing = false;  // feeding / submitting / polling from inside a delivery is refused
 };
 
 namespace {
@@ -460,6 +551,20 @@ int parse_chunk(kmws_decoder* dec, uint8_t* data, size_t len, Sink&& sink)
     return result;
 }
 
+// The descriptor of a frame that goes to the GPU, added to the list of the
+// buffer its payload lies in (offset off).  A checked frame takes the next
+// verdict byte of the job's stage: returned, else kNoSlot.
+uint32_t add_frame_desc(PinnedStage& stage, DescList& list, uint64_t off, uint32_t len, const kmws_decoder::Facts& f)
+{
+    if (!f.checked) {
+        list.add(off, len, f.dkey);
+        return kNoSlot;
+    }
+    const uint32_t slot = stage.utf8_slot();
+    list.add_checked(off, len, f.dkey, f.uv.w, slot);
+    return slot;
+}
+
 }  // namespace
 
 extern "C" {
@@ -517,66 +622,49 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
     if (!dec || (len && !data)) return KMWS_ERR_INVALID_PARAM;
     dec->pending.clear();
     dec->held.clear();
-    dec->chunk_descs.clear();
-    dec->chunk_views.clear();
     BorrowedStage bs(dec->device);  // given back when the call returns (the decoder may be gone by then)
     int chunk_pinned = -1;  // resolved at the first masked in-chunk frame
-    uint8_t* chunk_dv = nullptr;
-    uint8_t* chunk_base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(data) & ~(uintptr_t)15);
+    ExtraBuf& chunk = dec->chunk;
+    chunk.list.clear();
+    chunk.base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(data) & ~(uintptr_t)15);
+    chunk.span = (uint64_t)((data + len) - chunk.base);
+    chunk.dv = nullptr;
 
     auto sink = [&](const kmws_frame_hdr& h, uint8_t* payload, std::vector<uint8_t>* reasm) -> int {
-        Pending q{};
-        q.hdr = h;
-        const bool masked = h.mask && h.length;  // handleDataMask is a no-op otherwise (:293, :305)
-        uint32_t key;
-        std::memcpy(&key, h.maskey, 4);
-        // UTF-8 check: the parse-time half.  A checked frame with payload goes
-        // to the GPU whether it is masked or not (key 0: checked, not stored);
-        // an empty one needs no device work (rule (b) is decided here).
-        q.uv = dec->utf8_parse(h, payload, key);
-        q.slot = kNoSlot;
-        const bool checked = (q.uv.w & kUtf8Checked) != 0u && h.length;
-        const bool gpu = masked || checked;
-        const uint32_t dkey = masked ? key : 0u;
-        dec->pending.push_back(q);  // from here on the frame counts as parsed: a failure below drops it
-        Pending& qq = dec->pending.back();
-        if (gpu && !bs.get()) return bs.st;
-        if (checked) qq.slot = bs.s->utf8_slot();
-        auto stage_desc = [&](size_t off) {
-            if (checked) bs.s->add_desc_utf8(off, h.length, dkey, qq.uv.w, qq.slot);
-            else bs.s->add_desc(off, h.length, dkey);
+        // A frame with payload that is masked or checked goes to the GPU (key
+        // 0 when unmasked: checked, not stored).
+        const kmws_decoder::Facts f = dec->frame_facts(h, payload);
+        dec->pending.push_back(Pending{h, nullptr, 0, 0, kInChunk, f.uv, kNoSlot});
+        Pending& qq = dec->pending.back();  // from here on the frame counts as parsed: a failure below drops it
+        if (f.gpu() && !bs.get()) return bs.st;
+        auto stage_payload = [&]() -> kmws_status {
+            const kmws_status st = bs.s->reserve(h.length);
+            if (st != KMWS_OK) return st;
+            qq.stage_off = bs.s->append(payload, h.length);
+            qq.slot = add_frame_desc(*bs.s, bs.s->staged(), qq.stage_off, h.length, f);
+            return KMWS_OK;
         };
         if (!reasm) {
             qq.data_ptr = payload;
-            if (!gpu) {
-                qq.where = kInChunk;
-            } else {
+            if (f.gpu()) {
                 if (chunk_pinned < 0) {
-                    chunk_dv = chunk_base == dec->last_pageable ? nullptr
-                                                                : static_cast<uint8_t*>(device_view(chunk_base));
-                    chunk_pinned = chunk_dv != nullptr;
-                    if (!chunk_pinned) dec->last_pageable = chunk_base;
+                    if (chunk.base != dec->last_pageable) chunk.dv = static_cast<uint8_t*>(device_view(chunk.base));
+                    chunk_pinned = chunk.dv != nullptr;
+                    if (!chunk_pinned) dec->last_pageable = chunk.base;
                 }
                 if (chunk_pinned) {
-                    dec->chunk_descs.push_back(kmws_desc{(uint64_t)(payload - chunk_base), h.length, dkey});
-                    if (dec->utf8_check)
-                        dec->chunk_views.push_back(checked ? Utf8View{qq.slot, (qq.uv.w & 0xFFFFFFu) | kUtf8Checked}
-                                                           : Utf8View{0u, 0u});
-                    qq.where = masked ? kInChunkPinned : kInChunk;
+                    qq.slot = add_frame_desc(*bs.s, chunk.list, (uint64_t)(payload - chunk.base), h.length, f);
+                    if (f.masked) qq.where = kInChunkPinned;
                 } else {
-                    kmws_status st = bs.s->reserve(h.length);
+                    const kmws_status st = stage_payload();
                     if (st != KMWS_OK) return st;
-                    qq.stage_off = bs.s->append(payload, h.length);
-                    stage_desc(qq.stage_off);
                     // an unmasked checked frame is staged for the check only: the view stays on the chunk
-                    qq.where = masked ? kInChunkStaged : kInChunk;
+                    if (f.masked) qq.where = kInChunkStaged;
                 }
             }
-        } else if (gpu) {
-            kmws_status st = bs.s->reserve(h.length);
+        } else if (f.gpu()) {
+            const kmws_status st = stage_payload();
             if (st != KMWS_OK) return st;
-            qq.stage_off = bs.s->append(payload, h.length);
-            stage_desc(qq.stage_off);
             qq.where = kStagedMasked;
         } else {
             dec->held.emplace_back();
@@ -601,10 +689,8 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
     }
 
     // ---- GPU unmask of every masked payload of this call ----
-    if (bs.s && (bs.s->n_desc() || !dec->chunk_descs.empty())) {
-        const uint64_t chunk_span = (uint64_t)((data + len) - chunk_base);
-        kmws_status st = bs.s->run(chunk_base, chunk_span, &dec->chunk_descs, chunk_dv,
-                                   dec->chunk_views.empty() ? nullptr : &dec->chunk_views);
+    if (bs.s && (bs.s->n_desc() || !chunk.list.empty())) {
+        kmws_status st = bs.s->run(chunk);
         if (st != KMWS_OK) {
             drop_utf8();
             return st;
@@ -681,7 +767,7 @@ kmws_status kmws_mask_host_chain(const uint8_t key[KMWS_MASK_KEY_SIZE], uint8_t*
     }
     uint32_t k;
     std::memcpy(&k, key, 4);
-    s->add_desc(off, (uint32_t)total, k);
+    s->staged().add(off, (uint32_t)total, k);
     st = s->run();
     if (st != KMWS_OK) return st;
     pos = 0;
@@ -721,88 +807,32 @@ void kmws_host_free(void* p)
 // generation's iovecs once its ticket completed, and can fill and submit the
 // next generation meanwhile.  kmws_tx_batch_flush = submit + poll(wait).
 
-struct kmws_tx_batch {
-    BatchStream bstream;  // first: destroyed after every stage that uses it
-    struct Seg {
-        uint8_t* p;
-        size_t len;
-    };
-    struct Frame {
-        size_t seg0, nseg;  // range in segs
-        size_t bytes;
-        uint32_t key;
-    };
-    struct Gen {  // submitted: the stage with the launch in flight, segments to copy back
-        std::unique_ptr<PinnedStage> stage;
-        std::vector<Seg> segs;
-        std::vector<size_t> offs;  // staging offset per segment (SIZE_MAX: masked in the ring)
-        int64_t ticket;
-    };
+struct TxSeg {
+    uint8_t* p;
+    size_t len;
+};
+struct TxFrame {
+    size_t seg0, nseg;  // range in segs
+    size_t bytes;
+    uint32_t key;
+};
+struct TxGen {  // submitted: the stage with the launch in flight, segments to copy back
     std::unique_ptr<PinnedStage> stage;
-    std::vector<Seg> segs;
-    std::vector<Frame> frames;
-    size_t bytes = 0;
-    int device = 0;
-    uint8_t* ring = nullptr;  // caller's pinned send ring (optional)
-    uint8_t* ring_dv = nullptr;  // its device view, looked up once at attach
-    size_t ring_bytes = 0;
-    std::vector<kmws_desc> ring_descs;
-    std::deque<Gen> inflight;
-    std::vector<std::unique_ptr<PinnedStage>> spare;
-    int64_t next_ticket = 1, done_ticket = 0;
-    bool in_ring(const uint8_t* p, size_t n) const
-    {
-        return ring && p >= ring && n <= ring_bytes && (size_t)(p - ring) <= ring_bytes - n;
-    }
-    std::unique_ptr<PinnedStage> take_stage()
-    {
-        if (!spare.empty()) {
-            std::unique_ptr<PinnedStage> s = std::move(spare.back());
-            spare.pop_back();
-            return s;
-        }
-        std::unique_ptr<PinnedStage> s(new (std::nothrow) PinnedStage());
-        if (s && s->init(device, bstream.s) != KMWS_OK) s.reset();
-        return s;
-    }
-    // the stream and a few warm stages, made before the first loop iteration
-    kmws_status prepare(int dev)
-    {
-        device = dev;
-        kmws_status st = bstream.create(dev);
-        for (int i = 0; st == KMWS_OK && i < kWarmStages; ++i) {
-            std::unique_ptr<PinnedStage> s = take_stage();
-            if (!s) return KMWS_ERR_FAILED;
-            st = s->warm();
-            spare.push_back(std::move(s));
-        }
-        return st;
-    }
+    std::vector<TxSeg> segs;
+    std::vector<size_t> offs;  // staging offset per segment (SIZE_MAX: masked in the ring)
+    int64_t ticket;
 };
 
-kmws_tx_batch* kmws_tx_batch_create(int device)
-{
-    device = resolve_device(device);
-    kmws_tx_batch* b = new (std::nothrow) kmws_tx_batch();
-    if (!b) return nullptr;
-    if (b->prepare(device) != KMWS_OK) {
-        delete b;
-        return nullptr;
-    }
-    b->stage = b->take_stage();
-    if (!b->stage) {
-        delete b;
-        return nullptr;
-    }
-    return b;
-}
+struct kmws_tx_batch : GenQueue<TxGen> {
+    std::vector<TxSeg> segs;
+    std::vector<TxFrame> frames;
+    size_t bytes = 0;
+    int64_t next_ticket = 1, done_ticket = 0;
+};
 
-void kmws_tx_batch_destroy(kmws_tx_batch* b)
-{
-    if (!b) return;
-    for (auto& g : b->inflight) (void)g.stage->wait();  // no launch may outlive its pinned memory
-    delete b;
-}
+kmws_tx_batch* kmws_tx_batch_create(int device) { return batch_create<kmws_tx_batch>(device); }
+
+void kmws_tx_batch_destroy(kmws_tx_batch* b) { batch_destroy(b); }
 
 int kmws_tx_batch_pending(const kmws_tx_batch* b) { return b ? (int)b->frames.size() : 0; }
 
@@ -827,9 +857,9 @@ int kmws_tx_batch_add(kmws_tx_batch* b, const kmws_frame_hdr* hdr, uint8_t* cons
     if (h.mask && plen > 0) {
         uint32_t key;
         std::memcpy(&key, h.maskey, 4);
-        b->frames.push_back(kmws_tx_batch::Frame{b->segs.size(), 0, plen, key});
+        b->frames.push_back(TxFrame{b->segs.size(), 0, plen, key});
         for (size_t i = 0; i < nseg; ++i)
-            if (lens[i]) b->segs.push_back(kmws_tx_batch::Seg{segs[i], lens[i]});
+            if (lens[i]) b->segs.push_back(TxSeg{segs[i], lens[i]});
         b->frames.back().nseg = b->segs.size() - b->frames.back().seg0;
         b->bytes += plen;
     }
@@ -842,12 +872,7 @@ kmws_status kmws_tx_batch_attach_ring(kmws_tx_batch* b, uint8_t* ring, size_t ri
     if (!b || (ring && !ring_bytes)) return KMWS_ERR_INVALID_PARAM;
     // queued segments were classified already; a mask in flight may still be writing into the old ring
     if (!b->frames.empty() || !b->inflight.empty()) return KMWS_ERR_INVALID_STATE;
-    uint8_t* dv = ring ? static_cast<uint8_t*>(device_view(ring)) : nullptr;
-    if (ring && !dv) return KMWS_ERR_INVALID_PARAM;  // must be pinned
-    b->ring = ring;
-    b->ring_dv = dv;
-    b->ring_bytes = ring ? ring_bytes : 0;
-    return KMWS_OK;
+    return b->attach(ring, ring_bytes);
 }
 
 // One descriptor per segment, its key rotated by the frame bytes before it
@@ -863,51 +888,43 @@ static int64_t tx_submit(kmws_tx_batch* b, bool sync)
     std::unique_ptr<PinnedStage> next = b->take_stage();
     if (!next) return KMWS_ERR_FAILED;
     PinnedStage& s = *b->stage;
-    s.clear();
-    b->ring_descs.clear();
+    s.clear();  // the generation is staged here, not at kmws_tx_batch_add
+    b->ring.list.clear();
     size_t staged = 0;
-    for (const kmws_tx_batch::Seg& g : b->segs)
-        if (!b->in_ring(g.p, g.len)) staged += g.len + 16;
+    for (const TxSeg& g : b->segs)
+        if (!b->ring.holds(g.p, g.len)) staged += g.len + 16;
     kmws_status st = s.reserve(staged);
     std::vector<size_t> offs(b->segs.size(), SIZE_MAX);
     if (st == KMWS_OK) {
-        for (const kmws_tx_batch::Frame& fr : b->frames) {
+        for (const TxFrame& fr : b->frames) {
             size_t phase = 0;
             for (size_t i = fr.seg0; i < fr.seg0 + fr.nseg; ++i) {
-                const kmws_tx_batch::Seg& g = b->segs[i];
+                const TxSeg& g = b->segs[i];
                 const uint32_t key = __builtin_rotateright32(fr.key, 8u * (uint32_t)(phase & 3u));
-                if (b->in_ring(g.p, g.len)) {
-                    b->ring_descs.push_back(kmws_desc{(uint64_t)(g.p - b->ring), (uint32_t)g.len, key});
+                if (b->ring.holds(g.p, g.len)) {
+                    b->ring.list.add((uint64_t)(g.p - b->ring.base), (uint32_t)g.len, key);
                 } else {
                     uint8_t* dst = s.alloc(g.len, &offs[i]);
                     std::memcpy(dst, g.p, g.len);
-                    s.add_desc(offs[i], (uint32_t)g.len, key);
+                    s.staged().add(offs[i], (uint32_t)g.len, key);
                 }
                 phase += g.len;
             }
         }
-        if (sync)
-            st = b->ring_descs.empty() ? s.run() : s.run(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv);
-        else
-            st = b->ring_descs.empty() ? s.launch() : s.launch(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv);
+        st = b->launch(sync);
     }
     b->frames.clear();
-    b->ring_descs.clear();
     b->bytes = 0;
     if (st != KMWS_OK) {
         b->segs.clear();
-        s.clear();
-        b->spare.push_back(std::move(next));
+        b->restore(std::move(next));
         return st;
     }
-    kmws_tx_batch::Gen g;
-    g.stage = std::move(b->stage);
+    TxGen g;
     g.segs.swap(b->segs);
     g.offs.swap(offs);
     g.ticket = b->next_ticket++;
-    b->inflight.push_back(std::move(g));
-    b->stage = std::move(next);
-    return b->inflight.back().ticket;
+    return b->rotate(std::move(g), std::move(next)).ticket;
 }
 
 int64_t kmws_tx_batch_submit(kmws_tx_batch* b) { return tx_submit(b, false); }
@@ -917,7 +934,7 @@ int kmws_tx_batch_poll(kmws_tx_batch* b, int64_t ticket, int wait)
     if (!b || ticket < 0) return KMWS_ERR_INVALID_PARAM;
     kmws_status err = KMWS_OK;
     while (!b->inflight.empty() && b->inflight.front().ticket <= ticket) {
-        kmws_tx_batch::Gen& g = b->inflight.front();
+        TxGen& g = b->inflight.front();
         if (!wait && !g.stage->done()) break;
         const kmws_status st = g.stage->wait();
         if (st == KMWS_OK) {
@@ -927,8 +944,7 @@ int kmws_tx_batch_poll(kmws_tx_batch* b, int64_t ticket, int wait)
             err = st;
         }
         b->done_ticket = g.ticket;
-        g.stage->clear();
-        b->spare.push_back(std::move(g.stage));
+        b->retire(std::move(g.stage));
         b->inflight.pop_front();
     }
     if (err != KMWS_OK) return err;
@@ -963,29 +979,9 @@ int64_t kmws_tx_batch_flush(kmws_tx_batch* b)
 // submit at the end of an iteration and deliver at the next one: the GPU round
 // trip overlaps the loop's socket reads instead of stalling them.
 
-kmws_rx_batch* kmws_rx_batch_create(int device)
-{
-    device = resolve_device(device);
-    kmws_rx_batch* b = new (std::nothrow) kmws_rx_batch();
-    if (!b) return nullptr;
-    if (b->prepare(device) != KMWS_OK) {
-        delete b;
-        return nullptr;
-    }
-    b->stage = b->take_stage();
-    if (!b->stage) {
-        delete b;
-        return nullptr;
-    }
-    return b;
-}
+kmws_rx_batch* kmws_rx_batch_create(int device) { return batch_create<kmws_rx_batch>(device); }
 
-void kmws_rx_batch_destroy(kmws_rx_batch* b)
-{
-    if (!b) return;
-    for (auto& g : b->inflight) (void)g.stage->wait();  // no launch may outlive its pinned memory
-    delete b;
-}
+void kmws_rx_batch_destroy(kmws_rx_batch* b) { batch_destroy(b); }
 
 int kmws_decoder_feed_deferred(kmws_decoder* dec, kmws_rx_batch* b, const uint8_t* data, size_t len,
                                kmws_frame_cb cb, void* user)
@@ -996,45 +992,29 @@ int kmws_decoder_feed_deferred(kmws_decoder* dec, kmws_rx_batch* b, const uint8_
     // TcpConnection.cpp:229), so every payload is copied into the batch unless
     // it lies in the attached ring.  The parse does not write into the chunk.
     auto sink = [&](const kmws_frame_hdr& h, uint8_t* payload, std::vector<uint8_t>* reasm) -> int {
-        uint32_t key;
-        std::memcpy(&key, h.maskey, 4);
-        const bool masked = h.mask && h.length;
-        if (masked) b->pending_bytes += h.length;
-        // UTF-8 check: the parse-time half; a checked frame with payload gets a
-        // descriptor (key 0 when unmasked: checked, not stored) and a verdict byte
-        const Utf8StreamView uv = dec->utf8_parse(h, payload, key);
-        const bool checked = (uv.w & kUtf8Checked) != 0u && h.length;
-        uint32_t slot = kNoSlot;
-        const uint32_t dkey = masked ? key : 0u;
-        if (!reasm && b->ring && payload >= b->ring && payload + h.length <= b->ring + b->ring_bytes) {
-            // payload lies in the caller's pinned ring: unmasked there, no copy
-            if (masked || checked) {
-                if (checked) {
-                    slot = b->stage->utf8_slot();
-                    b->ring_views.resize(b->ring_descs.size(), Utf8View{0u, 0u});
-                    b->ring_views.push_back(Utf8View{slot, (uv.w & 0xFFFFFFu) | kUtf8Checked});
-                }
-                b->ring_descs.push_back(kmws_desc{(uint64_t)(payload - b->ring), h.length, dkey});
-            }
-            b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, 0, payload, true, uv, slot});
-            return KMWS_OK;
-        }
+        // a frame with payload that is masked or checked gets a descriptor
+        // (key 0 when unmasked: checked, not stored)
+        const kmws_decoder::Facts f = dec->frame_facts(h, payload);
+        if (f.masked) b->pending_bytes += h.length;
         // queued first: a frame the parse-time half has seen must be dropped
         // through rx_drop_utf8 if its payload cannot be staged
-        b->items.push_back(kmws_rx_batch::Item{dec, cb, user, h, 0, nullptr, true, uv, slot});
-        kmws_status st = b->stage->reserve(h.length);
+        b->items.push_back(RxItem{dec, cb, user, h, 0, nullptr, true, f.uv, kNoSlot});
+        RxItem& it = b->items.back();
+        if (!reasm && b->ring.holds(payload, h.length)) {
+            // payload lies in the caller's pinned ring: unmasked there, no copy
+            it.direct = payload;
+            const uint64_t off = (uint64_t)(payload - b->ring.base);
+            if (f.gpu()) it.slot = add_frame_desc(*b->stage, b->ring.list, off, h.length, f);
+            return KMWS_OK;
+        }
+        const kmws_status st = b->stage->reserve(h.length);
         if (st != KMWS_OK) {
-            utf8_stream_drop(dec->utf8, uv);
+            utf8_stream_drop(dec->utf8, f.uv);
             b->items.pop_back();
             return st;
         }
-        const size_t off = b->stage->append(payload, h.length);
-        b->items.back().off = off;
-        if (checked) {
-            slot = b->stage->utf8_slot();
-            b->items.back().slot = slot;
-            b->stage->add_desc_utf8(off, h.length, dkey, uv.w, slot);
-        } else if (masked) b->stage->add_desc(off, h.length, key);
+        it.off = b->stage->append(payload, h.length);
+        if (f.gpu()) it.slot = add_frame_desc(*b->stage, b->stage->staged(), it.off, h.length, f);
         return KMWS_OK;
     };
     return parse_chunk(dec, const_cast<uint8_t*>(data), len, sink);
@@ -1043,8 +1023,8 @@ int kmws_decoder_feed_deferred(kmws_decoder* dec, kmws_rx_batch* b, const uint8_
 // The frames of a generation that will never be delivered (its launch failed):
 // the parse-time half of their decoders has advanced past them, so their open
 // messages are no longer checkable until the next message head.  Live items
-// only: a discarded item's decoder may be gone (see Item::dec).
-static void rx_drop_utf8(std::vector<kmws_rx_batch::Item>& items)
+// only: a discarded item's decoder may be gone (see RxItem::dec).
+static void rx_drop_utf8(std::vector<RxItem>& items)
 {
     for (auto& it : items)
         if (it.live && (it.uv.w & kUtf8Checked)) utf8_stream_drop(it.dec->utf8, it.uv);
@@ -1052,7 +1032,7 @@ static void rx_drop_utf8(std::vector<kmws_rx_batch::Item>& items)
 
 // The delivery-time half for a whole generation, before its first callback:
 // hdr.reserved holds the verdict while the frame's callback runs.
-static void rx_verdicts(std::vector<kmws_rx_batch::Item>& items, const PinnedStage& stage)
+static void rx_verdicts(std::vector<RxItem>& items, const PinnedStage& stage)
 {
     for (auto& it : items)
         if (it.live && (it.uv.w & kUtf8Checked))
@@ -1063,12 +1043,7 @@ static void rx_verdicts(std::vector<kmws_rx_batch::Item>& items, const PinnedSta
 kmws_status kmws_rx_batch_attach_ring(kmws_rx_batch* b, uint8_t* ring, size_t bytes)
 {
     if (!b || b->flushing || !b->items.empty() || !b->inflight.empty()) return KMWS_ERR_INVALID_STATE;
-    uint8_t* dv = ring && bytes ? static_cast<uint8_t*>(device_view(ring)) : nullptr;
-    if (ring && !dv) return KMWS_ERR_INVALID_PARAM;  // must be pinned
-    b->ring = ring;
-    b->ring_dv = dv;
-    b->ring_bytes = ring ? bytes : 0;
-    return KMWS_OK;
+    return b->attach(ring, bytes);
 }
 
 int kmws_rx_batch_pending(const kmws_rx_batch* b) { return b ? (int)b->items.size() : 0; }
@@ -1099,28 +1074,19 @@ static int rx_submit(kmws_rx_batch* b, bool sync)
     if (b->items.empty()) return 0;
     std::unique_ptr<PinnedStage> next = b->take_stage();
     if (!next) return KMWS_ERR_FAILED;
-    // a generation with a checked frame launches the pieces kernel with the
-    // check (never the resident worker); any other goes as it always went
-    const std::vector<Utf8View>* rv = b->ring_views.empty() ? nullptr : &b->ring_views;
-    kmws_status st = sync ? b->stage->run(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv, rv)
-                          : b->stage->launch(b->ring, b->ring_bytes, &b->ring_descs, b->ring_dv, kResMaxBytesAsync, rv);
-    b->ring_descs.clear();
-    b->ring_views.clear();
+    const kmws_status st = b->launch(sync);  // the payloads were staged at feed time
     b->pending_bytes = 0;
     if (st != KMWS_OK) {
         // nothing of this generation can be delivered masked: drop it
         rx_drop_utf8(b->items);
         b->items.clear();
-        b->stage->clear();
-        b->spare.push_back(std::move(next));
+        b->restore(std::move(next));
         return st;
     }
     const int n = (int)b->items.size();
-    kmws_rx_batch::Gen g;
-    g.stage = std::move(b->stage);
+    RxGen g;
     g.items.swap(b->items);
-    b->inflight.push_back(std::move(g));
-    b->stage = std::move(next);
+    b->rotate(std::move(g), std::move(next));
     return n;
 }
 
@@ -1133,18 +1099,17 @@ int kmws_rx_batch_poll(kmws_rx_batch* b, int wait)
     int delivered = 0;
     kmws_status err = KMWS_OK;
     while (!b->inflight.empty()) {
-        kmws_rx_batch::Gen& g = b->inflight.front();
+        RxGen& g = b->inflight.front();
         if (!wait && !g.stage->done()) break;
         const kmws_status st = g.stage->wait();
-        std::vector<kmws_rx_batch::Item> items;
+        std::vector<RxItem> items;
         items.swap(g.items);
         std::unique_ptr<PinnedStage> stage = std::move(g.stage);
         b->inflight.pop_front();
         if (st != KMWS_OK) {  // the launch failed: these payloads are still masked, never delivered
             err = st;
             rx_drop_utf8(items);
-            stage->clear();
-            b->spare.push_back(std::move(stage));
+            b->retire(std::move(stage));
             continue;
         }
         rx_verdicts(items, *stage);  // before the first callback: every live item's decoder is alive
@@ -1161,8 +1126,7 @@ int kmws_rx_batch_poll(kmws_rx_batch* b, int wait)
         }
         b->delivering = nullptr;
         b->flushing = false;
-        stage->clear();
-        b->spare.push_back(std::move(stage));
+        b->retire(std::move(stage));
     }
     return err != KMWS_OK ? err : delivered;
 }

@@ -55,17 +55,65 @@ inline size_t grow(size_t need, size_t have)
     return c;
 }
 
+// A checked frame's view: slot = its verdict byte, lookback = the 24 bits
+// before its first payload byte.
+inline Utf8View checked_view(uint32_t slot, uint32_t lookback)
+{
+    return Utf8View{slot, (lookback & 0xFFFFFFu) | kUtf8Checked};
+}
+
+// Descriptors of one buffer, with a view beside each once one of them is
+// checked: `views` stays empty until the first checked descriptor and is padded
+// lazily, so it may be shorter than `descs` (the rest: unchecked).
+struct DescList {
+    std::vector<kmws_desc> descs;
+    std::vector<Utf8View> views;
+    void add(uint64_t off, uint32_t len, uint32_t key) { descs.push_back(kmws_desc{off, len, key}); }
+    void add_checked(uint64_t off, uint32_t len, uint32_t key, uint32_t lookback, uint32_t slot)
+    {
+        views.resize(descs.size(), Utf8View{0u, 0u});
+        add(off, len, key);
+        views.push_back(checked_view(slot, lookback));
+    }
+    const Utf8View* views_or_null() const { return views.empty() ? nullptr : views.data(); }
+    size_t size() const { return descs.size(); }
+    bool empty() const { return descs.empty(); }
+    void clear()
+    {
+        descs.clear();
+        views.clear();
+    }
+};
+
+// Descriptors that target a pinned buffer other than a stage's own area: a
+// caller's chunk, or the ring attached to a batch.  Offsets are relative to
+// `base` and must end within `span` bytes of it.  dv: the device view of base
+// if the owner has it (a ring attached once), else launch() looks it up
+// (hipPointerGetAttributes).  An empty list means "no extra".
+struct ExtraBuf {
+    uint8_t* base = nullptr;
+    uint64_t span = 0;
+    uint8_t* dv = nullptr;
+    DescList list;
+    // Is [p, p + n) inside the buffer?
+    bool holds(const uint8_t* p, size_t n) const
+    {
+        return base && p >= base && n <= span && (uint64_t)(p - base) <= span - n;
+    }
+};
+
 // A batch of payloads unmasked in place by the GPU.  Payloads are appended to
 // a pinned host area (16-B aligned starts); launch() posts them as one job on
 // the calling thread's slot of the resident worker when they fit one, else
 // enqueues the pieces kernel on the pinned area itself (zero-copy over PCIe)
 // on the stage's own stream and records its completion event; done() / wait()
 // follow whichever ran; run() = launch() + wait.  An optional second
-// batch of descriptors can target another pinned buffer (a caller's registered
-// receive or send ring).  The asynchronous rx / tx batches keep one stage per
-// generation in flight (kmws_decoder.cpp).
+// batch of descriptors can target another pinned buffer (an ExtraBuf: a
+// caller's pinned chunk, or its registered receive or send ring).  The
+// asynchronous rx / tx batches keep one stage per generation in flight
+// (kmws_decoder.cpp).
 // UTF-8 check (kmws_decoder_set_utf8_check): a descriptor added with
-// add_desc_utf8, or an extra one whose view is checked, makes the job a checked
+// staged().add_checked, or an extra one whose view is checked, makes the job a checked
 // one, with a view per descriptor and one verdict byte per checked frame
 // (utf8_slot / utf8_bad) in the stage's pinned arrays.  It is posted to the
 // resident worker when it has at most kResMaxDescs payloads and at most
@@ -169,37 +217,26 @@ public:
         return h_ + *off;
     }
     uint8_t* data() { return h_; }
-    void add_desc(uint64_t off, uint32_t len, uint32_t key) { descs_.push_back(kmws_desc{off, len, key}); }
-    // A checked frame's payload: lookback = the 24 bits before its first byte,
-    // slot = its verdict byte (utf8_slot()).  key 0: checked only, not stored.
-    void add_desc_utf8(uint64_t off, uint32_t len, uint32_t key, uint32_t lookback, uint32_t slot)
-    {
-        views_.resize(descs_.size(), Utf8View{0u, 0u});
-        descs_.push_back(kmws_desc{off, len, key});
-        views_.push_back(Utf8View{slot, (lookback & 0xFFFFFFu) | kUtf8Checked});
-    }
+    // The staged descriptors.  add_checked: a checked frame's payload, slot =
+    // its verdict byte (utf8_slot()); key 0: checked only, not stored.
+    DescList& staged() { return own_; }
     // The next verdict byte of this job: one per checked, non-empty frame, staged or extra.
     uint32_t utf8_slot() { return n_slots_++; }
     // After wait(): the payload pass found a byte of the slot's frame that the rule rejects.
     bool utf8_bad(uint32_t slot) const { return h_verdict_ && slot < n_slots_ && slot < desc_cap_ && h_verdict_[slot] != 0; }
-    size_t n_desc() const { return descs_.size(); }
+    size_t n_desc() const { return own_.size(); }
     void clear()
     {
         len_ = 0;
-        descs_.clear();
-        views_.clear();
+        own_.clear();
         n_slots_ = 0;
     }
 
-    // Unmask every staged descriptor (and `extra` over `extra_base`, a pinned
-    // buffer of extra_span bytes, if given), then wait for the GPU: launch() +
-    // wait().  extra_dv: the device view of extra_base if the caller has it (a
-    // ring attached once); else it is looked up here (hipPointerGetAttributes).
-    kmws_status run(uint8_t* extra_base = nullptr, uint64_t extra_span = 0,
-                    const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr,
-                    const std::vector<Utf8View>* extra_views = nullptr)
+    // Unmask every staged descriptor (and those of `extra` in its buffer), then
+    // wait for the GPU: launch() + wait().
+    kmws_status run(const ExtraBuf& extra = ExtraBuf())
     {
-        kmws_status st = launch(extra_base, extra_span, extra, extra_dv, kResMaxBytes, extra_views);
+        kmws_status st = launch(extra, kResMaxBytes);
         if (st != KMWS_OK) return st;
         return wait();
     }
@@ -262,25 +299,23 @@ public:
     // read-back) with its completion event recorded.
     // max_res_bytes: the largest job posted on the worker (a synchronous run()
     // keeps kResMaxBytes: one workgroup is slower than a launch's many above it).
-    // extra_views: a view per extra descriptor (shorter: the rest unchecked), or
-    // nullptr; a job with a checked frame is posted with its views and the
-    // zeroed verdict bytes if it has at most min(max_res_bytes,
-    // kResMaxBytesChecked) bytes, else launches the pieces kernel with the check.
-    kmws_status launch(uint8_t* extra_base = nullptr, uint64_t extra_span = 0,
-                       const std::vector<kmws_desc>* extra = nullptr, uint8_t* extra_dv = nullptr,
-                       uint64_t max_res_bytes = kResMaxBytesAsync, const std::vector<Utf8View>* extra_views = nullptr)
+    // A view of extra.list checks its descriptor; a job with a checked frame,
+    // staged or extra, is posted with its views and the zeroed verdict bytes if
+    // it has at most min(max_res_bytes, kResMaxBytesChecked) bytes, else
+    // launches the pieces kernel with the check.
+    kmws_status launch(const ExtraBuf& extra = ExtraBuf(), uint64_t max_res_bytes = kResMaxBytesAsync)
     {
-        const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
+        const std::vector<kmws_desc>& d2 = extra.list.descs;
+        const std::vector<Utf8View>& v2 = extra.list.views;
+        const size_t n1 = own_.size(), n2 = d2.size();
         if (n1 + n2 == 0) return KMWS_OK;
         if (launched_) return KMWS_ERR_INVALID_STATE;
-        bool checked = !views_.empty();
-        if (extra_views)
-            for (size_t i = 0; i < extra_views->size() && i < n2; ++i) checked |= ((*extra_views)[i].w & kUtf8Checked) != 0u;
-        if (!checked) extra_views = nullptr;
-        for (size_t i = 0; i < n2; ++i)
-            if ((*extra)[i].off + (*extra)[i].len > extra_span) return KMWS_ERR_INVALID_PARAM;
-        if (n2 && !extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
-        if (n2 && !extra_dv) return KMWS_ERR_INVALID_PARAM;  // must be pinned
+        bool checked = !own_.views.empty();
+        for (size_t i = 0; i < v2.size() && i < n2; ++i) checked |= (v2[i].w & kUtf8Checked) != 0u;
+        for (const kmws_desc& x : d2)
+            if (x.off + x.len > extra.span) return KMWS_ERR_INVALID_PARAM;
+        uint8_t* dv2 = n2 && !extra.dv ? static_cast<uint8_t*>(device_view(extra.base)) : extra.dv;
+        if (n2 && !dv2) return KMWS_ERR_INVALID_PARAM;  // must be pinned
         if (n1 && !dv_h_) return KMWS_ERR_FAILED;
         if (n1 + n2 <= (size_t)kResMaxDescs && (!checked || n_slots_ <= n1 + n2)) {
             // a checked job: its views, and the stage's verdict bytes zeroed
@@ -288,44 +323,31 @@ public:
             if (checked) {
                 const kmws_status es = ensure_host(n1 + n2, 0);
                 if (es != KMWS_OK) return es;
-                views_.resize(n1, Utf8View{0u, 0u});
+                own_.views.resize(n1, Utf8View{0u, 0u});
                 std::memset(h_verdict_, 0, n1 + n2);
-                ck = ResidentCheck{n1 ? views_.data() : nullptr,
-                                   extra_views ? extra_views->data() : nullptr,
-                                   extra_views ? extra_views->size() : 0,
-                                   dv_verdict_,
-                                   n_slots_,
-                                   h_,
-                                   extra_base};
+                ck = ResidentCheck{own_.views_or_null(), extra.list.views_or_null(), v2.size(), dv_verdict_,
+                                   n_slots_, h_, extra.base};
             }
-            const kmws_status st = resident_post(device_, descs_.data(), dv_h_, n1, n2 ? extra->data() : nullptr,
-                                                 extra_dv, n2, &res_,
+            const kmws_status st = resident_post(device_, own_.descs.data(), dv_h_, n1, n2 ? d2.data() : nullptr, dv2,
+                                                 n2, &res_,
                                                  checked ? std::min(max_res_bytes, kResMaxBytesChecked) : max_res_bytes,
                                                  checked ? &ck : nullptr);
             if (st == KMWS_OK) {  // kept for a launch if the worker withdraws the job
-                saved_base_ = extra_base;
-                saved_span_ = extra_span;
-                saved_dv_ = extra_dv;
-                saved_extra_.assign(extra ? extra->begin() : saved_extra_.end(), extra ? extra->end() : saved_extra_.end());
+                saved_ = extra;
+                saved_.dv = dv2;
                 saved_checked_ = checked;
-                saved_views_.clear();
-                if (extra_views) saved_views_ = *extra_views;
                 res_pending_ = true;
                 launched_ = true;
                 return KMWS_OK;
             }
             if (st != KMWS_ERR_NOT_SUPPORTED) return st;
         }
-        return launch_kernels(extra_base, extra_span, extra, extra_dv, checked, extra_views);
+        return launch_kernels(extra, dv2, checked);
     }
 
 private:
-    kmws_status launch_saved()
-    {
-        // the call launch() makes, with the job's own check and views
-        return launch_kernels(saved_base_, saved_span_, saved_extra_.empty() ? nullptr : &saved_extra_, saved_dv_,
-                              saved_checked_, saved_checked_ && !saved_views_.empty() ? &saved_views_ : nullptr);
-    }
+    // the call launch() makes, with the withdrawn job's own extra and check
+    kmws_status launch_saved() { return launch_kernels(saved_, saved_.dv, saved_checked_); }
 
     // The device may still write the staging area (a resident job that timed
     // out) and, if the job was a checked one, the verdict bytes in the
@@ -337,8 +359,7 @@ private:
         dv_h_ = nullptr;
         cap_ = 0;
         len_ = 0;
-        descs_.clear();
-        views_.clear();
+        own_.clear();
         n_slots_ = 0;
         h_desc_ = nullptr;
         dv_desc_ = nullptr;
@@ -347,56 +368,95 @@ private:
         desc_cap_ = 0;
     }
 
-    kmws_status launch_kernels(uint8_t* extra_base, uint64_t extra_span, const std::vector<kmws_desc>* extra,
-                               uint8_t* extra_dv, bool checked = false,
-                               const std::vector<Utf8View>* extra_views = nullptr)
+    // One record per piece of x, which is descriptor idx of its launch.  The
+    // checked launch's record carries the four still-masked bytes before each
+    // piece j >= 1 -- read here, from host memory, before anything is launched.
+    static PieceRec* add_pieces(PieceRec* out, const uint8_t*, const kmws_desc& x, uint32_t idx)
     {
-        const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
-        if (n1 + n2 == 0) return KMWS_OK;
+        for (uint64_t j = 0, c = piece_count(x.off, x.len); j < c; ++j) *out++ = PieceRec{idx, (uint32_t)j};
+        return out;
+    }
+    static PieceRecEdge* add_pieces(PieceRecEdge* out, const uint8_t* host, const kmws_desc& x, uint32_t idx)
+    {
+        for (uint64_t j = 0, c = piece_count(x.off, x.len); j < c; ++j) {
+            uint32_t edge = 0;
+            if (j) std::memcpy(&edge, host + 16 * ((x.off >> 4) + j * kPieceWords) - 4, 4);
+            *out++ = PieceRecEdge{idx, (uint32_t)j, edge};
+        }
+        return out;
+    }
+    // The pinned descriptor and piece arrays of a launch: the staged descriptors
+    // with their pieces, then the extra ones rebased by delta onto eb, the extra
+    // buffer's aligned base; their records index from the first extra descriptor
+    // (the second launch gets dv_desc_ + n1).
+    template <class Rec>
+    void write_lists(const std::vector<kmws_desc>& d2, const uint8_t* eb, uint64_t delta)
+    {
+        const size_t n1 = own_.size();
+        Rec* out = reinterpret_cast<Rec*>(h_piece_);
+        if (n1) std::memcpy(h_desc_, own_.descs.data(), n1 * sizeof(kmws_desc));
+        for (size_t i = 0; i < n1; ++i) out = add_pieces(out, h_, own_.descs[i], (uint32_t)i);
+        for (size_t i = 0; i < d2.size(); ++i) {
+            kmws_desc x = d2[i];
+            x.off += delta;
+            h_desc_[n1 + i] = x;
+            out = add_pieces(out, eb, x, (uint32_t)i);
+        }
+    }
+
+    // Launches the pieces kernel over the staged descriptors, then over the
+    // extra ones (already checked by launch(); extra_dv: the buffer's device
+    // view), and records the completion event.  checked: the kernel with the
+    // UTF-8 check, which also gets a view per descriptor, the zeroed verdict
+    // bytes and the edge word per piece; a job without a checked frame copies
+    // and zeroes none of that.
+    kmws_status launch_kernels(const ExtraBuf& extra, uint8_t* extra_dv, bool checked)
+    {
+        const std::vector<kmws_desc>& d2 = extra.list.descs;
+        const std::vector<Utf8View>& v2 = extra.list.views;
+        const size_t n1 = own_.size(), n2 = d2.size();
         DevGuard g(device_);
         // the extra buffer's 16-B aligned base, descriptors rebased onto it
-        uint8_t* eb = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(extra_base) & ~(uintptr_t)15);
-        const uint64_t delta = (uint64_t)(extra_base - eb);
+        uint8_t* eb = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(extra.base) & ~(uintptr_t)15);
+        const uint64_t delta = (uint64_t)(extra.base - eb);
         uint64_t p1 = 0, p2 = 0, bytes = 0;
-        for (const kmws_desc& x : descs_) {
+        for (const kmws_desc& x : own_.descs) {
             p1 += piece_count(x.off, x.len);
             bytes += x.len;
         }
-        for (size_t i = 0; i < n2; ++i) {
-            const kmws_desc& x = (*extra)[i];
-            if (x.off + x.len > extra_span) return KMWS_ERR_INVALID_PARAM;
+        for (const kmws_desc& x : d2) {
             p2 += piece_count(x.off + delta, x.len);
             bytes += x.len;
         }
         if (p1 + p2 > 0x7FFFFFFFull) return KMWS_ERR_INVALID_PARAM;
         kmws_status st = ensure_host(n1 + n2, p1 + p2);
         if (st != KMWS_OK) return st;
-        if (checked) return launch_checked(extra_base, eb, delta, extra, extra_dv, extra_views, p1, p2, bytes);
-        std::memcpy(h_desc_, descs_.data(), n1 * sizeof(kmws_desc));
-        size_t k = 0;
-        for (size_t i = 0; i < n1; ++i)
-            for (uint64_t j = 0, c = piece_count(descs_[i].off, descs_[i].len); j < c; ++j)
-                h_piece_[k++] = PieceRec{(uint32_t)i, (uint32_t)j};
-        for (size_t i = 0; i < n2; ++i) {
-            kmws_desc x = (*extra)[i];
-            x.off += delta;
-            h_desc_[n1 + i] = x;
-            for (uint64_t j = 0, c = piece_count(x.off, x.len); j < c; ++j)
-                h_piece_[k++] = PieceRec{(uint32_t)i, (uint32_t)j};
+        if (checked) {
+            if (n_slots_ > n1 + n2) return KMWS_ERR_INVALID_STATE;  // a slot without its descriptor
+            own_.views.resize(n1, Utf8View{0u, 0u});
+            if (n1) std::memcpy(h_view_, own_.views.data(), n1 * sizeof(Utf8View));
+            for (size_t i = 0; i < n2; ++i) {  // a view whose slot is not below n_slots_ is unchecked
+                Utf8View v = i < v2.size() ? v2[i] : Utf8View{0u, 0u};
+                if (!(v.w & kUtf8Checked) || v.slot >= n_slots_) v = Utf8View{0u, 0u};
+                h_view_[n1 + i] = v;
+            }
+            std::memset(h_verdict_, 0, n1 + n2);
+            write_lists<PieceRecEdge>(d2, eb, delta);
+        } else {
+            write_lists<PieceRec>(d2, eb, delta);
         }
-        if (p1) {
-            uint8_t* dv = dv_h_;  // device view of the staging area, taken when it was allocated
-            if (!dv) return KMWS_ERR_FAILED;
-            st = launch_unmask_pieces(dv, dv_desc_, dv_piece_, (uint32_t)p1, stream_);
-            if (st != KMWS_OK) return st;
-        }
-        if (p2) {
-            if (!extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
-            if (!extra_dv) return KMWS_ERR_INVALID_PARAM;
-            uint8_t* dv = extra_dv - delta;  // the aligned base's view (one mapping per allocation)
-            st = launch_unmask_pieces(dv, dv_desc_ + n1, dv_piece_ + p1, (uint32_t)p2, stream_);
-            if (st != KMWS_OK) return st;
-        }
+        // np pieces from piece q0 on, of the descriptors from d0 on, in the buffer at `base`
+        auto go = [&](uint8_t* base, size_t d0, uint64_t q0, uint64_t np) {
+            return checked ? launch_unmask_pieces_utf8(base, dv_desc_ + d0, dv_view_ + d0,
+                                                       reinterpret_cast<PieceRecEdge*>(dv_piece_) + q0, (uint32_t)np,
+                                                       dv_verdict_, stream_)
+                           : launch_unmask_pieces(base, dv_desc_ + d0, dv_piece_ + q0, (uint32_t)np, stream_);
+        };
+        // the staging area's device view was taken when it was allocated; the
+        // extra buffer goes by its aligned base's view (one mapping per allocation)
+        if (p1) st = go(dv_h_, 0, 0, p1);
+        if (st == KMWS_OK && p2) st = go(extra_dv - delta, n1, p1, p2);
+        if (st != KMWS_OK) return st;
         if (hipEventRecord(done_, stream_) != hipSuccess) return KMWS_ERR_FAILED;
         // spin for about twice what the job should take (a launch's ~20 us, then
         // the payload over PCIe at ~8 GB/s each way), at least 1 ms -- a kernel
@@ -408,63 +468,6 @@ private:
         launched_ = true;
         return KMWS_OK;
     }
-
-    // The checked form of launch_kernels (after its argument checks and
-    // ensure_host): descriptors, views and zeroed verdict bytes, and a piece list
-    // whose records carry the four still-masked bytes before each piece j >= 1
-    // -- read here, from host memory, before anything is launched.
-    kmws_status launch_checked(uint8_t* extra_base, uint8_t* eb, uint64_t delta, const std::vector<kmws_desc>* extra,
-                               uint8_t* extra_dv, const std::vector<Utf8View>* extra_views, uint64_t p1, uint64_t p2,
-                               uint64_t bytes)
-    {
-        const size_t n1 = descs_.size(), n2 = extra ? extra->size() : 0;
-        if (n_slots_ > n1 + n2) return KMWS_ERR_INVALID_STATE;  // a slot without its descriptor
-        views_.resize(n1, Utf8View{0u, 0u});
-        if (n1) {
-            std::memcpy(h_desc_, descs_.data(), n1 * sizeof(kmws_desc));
-            std::memcpy(h_view_, views_.data(), n1 * sizeof(Utf8View));
-        }
-        std::memset(h_verdict_, 0, n1 + n2);
-        PieceRecEdge* pe = reinterpret_cast<PieceRecEdge*>(h_piece_);
-        auto add_pieces = [&](const uint8_t* host, const kmws_desc& x, uint32_t idx, size_t k) {
-            for (uint64_t j = 0, c = piece_count(x.off, x.len); j < c; ++j) {
-                uint32_t edge = 0;
-                if (j) std::memcpy(&edge, host + 16 * ((x.off >> 4) + j * kPieceWords) - 4, 4);
-                pe[k++] = PieceRecEdge{idx, (uint32_t)j, edge};
-            }
-            return k;
-        };
-        size_t k = 0;
-        for (size_t i = 0; i < n1; ++i) k = add_pieces(h_, descs_[i], (uint32_t)i, k);
-        for (size_t i = 0; i < n2; ++i) {
-            kmws_desc x = (*extra)[i];
-            x.off += delta;
-            h_desc_[n1 + i] = x;
-            Utf8View v = extra_views && i < extra_views->size() ? (*extra_views)[i] : Utf8View{0u, 0u};
-            if (!(v.w & kUtf8Checked) || v.slot >= n_slots_) v = Utf8View{0u, 0u};
-            h_view_[n1 + i] = v;
-            k = add_pieces(eb, x, (uint32_t)i, k);
-        }
-        kmws_status st = KMWS_OK;
-        if (p1) {
-            if (!dv_h_) return KMWS_ERR_FAILED;
-            st = launch_unmask_pieces_utf8(dv_h_, dv_desc_, dv_view_, dv_piece_edge(), (uint32_t)p1, dv_verdict_,
-                                           stream_);
-            if (st != KMWS_OK) return st;
-        }
-        if (p2) {
-            if (!extra_dv) extra_dv = static_cast<uint8_t*>(device_view(extra_base));
-            if (!extra_dv) return KMWS_ERR_INVALID_PARAM;
-            st = launch_unmask_pieces_utf8(extra_dv - delta, dv_desc_ + n1, dv_view_ + n1, dv_piece_edge() + p1,
-                                           (uint32_t)p2, dv_verdict_, stream_);
-            if (st != KMWS_OK) return st;
-        }
-        if (hipEventRecord(done_, stream_) != hipSuccess) return KMWS_ERR_FAILED;
-        spin_us_ = std::min<uint64_t>(2000, std::max<uint64_t>(1000, 2 * (20 + (bytes >> 13))));  // as launch_kernels
-        launched_ = true;
-        return KMWS_OK;
-    }
-    PieceRecEdge* dv_piece_edge() const { return reinterpret_cast<PieceRecEdge*>(dv_piece_); }
 
     // Pinned descriptor and piece arrays (and their device views) for nd / np
     // entries.  Each allocation also holds what the checked launch adds for its
@@ -527,19 +530,14 @@ private:
     bool launched_ = false;
     bool res_pending_ = false;  // launched_ on the resident worker: res_ says which job
     ResidentJob res_;
-    uint8_t* saved_base_ = nullptr;  // extra of a resident job, for launch_saved()
-    uint64_t saved_span_ = 0;
-    uint8_t* saved_dv_ = nullptr;
-    std::vector<kmws_desc> saved_extra_;
-    bool saved_checked_ = false;          // ... and its check, with the extra descriptors' views
-    std::vector<Utf8View> saved_views_;
+    ExtraBuf saved_;              // a copy of a resident job's extra, for launch_saved()
+    bool saved_checked_ = false;  // ... and its check
     uint64_t spin_us_ = 1000;
     uint8_t* h_ = nullptr;
     uint8_t* dv_h_ = nullptr;
     size_t cap_ = 0, len_ = 0;
-    std::vector<kmws_desc> descs_;
-    std::vector<Utf8View> views_;  // empty: no staged descriptor is checked; else one per descriptor so far
-    uint32_t n_slots_ = 0;         // verdict bytes handed out (utf8_slot)
+    DescList own_;          // the staged descriptors: offsets into h_
+    uint32_t n_slots_ = 0;  // verdict bytes handed out (utf8_slot)
     kmws_desc* h_desc_ = nullptr;   // pinned, read by the kernel over PCIe
     kmws_desc* dv_desc_ = nullptr;  // its device view
     Utf8View* h_view_ = nullptr;    // behind the descriptors, in their allocation

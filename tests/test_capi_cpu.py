@@ -295,6 +295,62 @@ def test_copy_entries_reject_bad_arguments_before_any_device_work():
     assert got == [(name, i, want) for i, (name, _, want) in enumerate(rows)]
 
 
+def test_batch_entries_with_a_null_handle():
+    """The status of every rx / tx batch entry and of kmws_decoder_feed_deferred
+    for a NULL handle, and of kmws_tx_batch_poll for a negative ticket.  The two
+    attach entries differ (rx: INVALID_STATE, tx: INVALID_PARAM).  No row
+    dereferences a handle, so the table holds with and without a device."""
+    import ctypes as C
+    L = kmws.lib()
+    bad, state = kmws.ERR_INVALID_PARAM, kmws.ERR_INVALID_STATE
+    fake = C.c_void_p(4096)  # never dereferenced: the rows that pass it fail on another argument first
+    hdr = kmws.Header(fin=1, opcode=2, mask=1, maskey=b"abcd").to_c()
+    seg = (C.c_uint8 * 4)()
+    segs, lens = (C.c_void_p * 1)(C.addressof(seg)), (C.c_size_t * 1)(4)
+    out = (C.c_uint8 * kmws.MAX_HEADER_SIZE)()
+    cb = kmws.FRAME_CB(lambda hp, p, n, u: 0)
+    dec = L.kmws_decoder_create(kmws.SERVER, 0)
+    assert dec
+    rows = [
+        ("kmws_rx_batch_pending", [None], 0),
+        ("kmws_rx_batch_pending_bytes", [None], 0),
+        ("kmws_rx_batch_inflight", [None], 0),
+        ("kmws_rx_batch_submit", [None], bad),
+        ("kmws_rx_batch_poll", [None, 0], bad),
+        ("kmws_rx_batch_poll", [None, 1], bad),
+        ("kmws_rx_batch_flush", [None], bad),
+        ("kmws_rx_batch_attach_ring", [None, None, 0], state),
+        ("kmws_rx_batch_attach_ring", [None, fake, 4096], state),
+        ("kmws_rx_batch_discard", [None, None], None),
+        ("kmws_rx_batch_discard", [None, dec], None),
+        ("kmws_rx_batch_destroy", [None], None),
+        ("kmws_tx_batch_pending", [None], 0),
+        ("kmws_tx_batch_submit", [None], bad),
+        ("kmws_tx_batch_poll", [None, 0, 0], bad),
+        ("kmws_tx_batch_poll", [None, 1, 1], bad),
+        ("kmws_tx_batch_poll", [None, -1, 0], bad),
+        ("kmws_tx_batch_poll", [fake, -1, 0], bad),
+        ("kmws_tx_batch_poll", [fake, -(1 << 62), 1], bad),
+        ("kmws_tx_batch_flush", [None], bad),
+        ("kmws_tx_batch_add", [None, C.byref(hdr), segs, lens, 1, out], bad),
+        ("kmws_tx_batch_attach_ring", [None, None, 0], bad),
+        ("kmws_tx_batch_attach_ring", [None, fake, 4096], bad),
+        ("kmws_tx_batch_destroy", [None], None),
+        ("kmws_decoder_feed_deferred", [None, None, seg, 4, cb, None], bad),
+        ("kmws_decoder_feed_deferred", [None, fake, seg, 4, cb, None], bad),
+        ("kmws_decoder_feed_deferred", [dec, None, seg, 4, cb, None], bad),
+        ("kmws_decoder_feed_deferred", [dec, None, None, 0, cb, None], bad),
+        ("kmws_decoder_feed_deferred", [dec, fake, None, 4, cb, None], bad),  # data NULL with a length
+    ]
+    try:
+        got = [(name, i, getattr(L, name)(*args)) for i, (name, args, _) in enumerate(rows)]
+    finally:
+        L.kmws_decoder_destroy(dec)
+    assert got == [(name, i, want) for i, (name, _, want) in enumerate(rows)]
+    every = {n for n in kmws.EXPORTS if n.startswith(("kmws_rx_batch_", "kmws_tx_batch_"))}
+    assert every - {r[0] for r in rows} == {"kmws_rx_batch_create", "kmws_tx_batch_create"}
+
+
 def test_copy_workspace_size_follows_the_copy_form():
     """kmws_copy_workspace_size (no device needed): below a 16 KiB mean region
     bound (dst_cap / n) the chunk form's 8 B per 4 KiB output chunk, from it the
