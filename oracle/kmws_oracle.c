@@ -10,17 +10,17 @@
  * reference checkout).  No reference source is copied: the byte semantics are
  * restated in plain C, including the reference's quirks.
  *
- * PARITY UNPINNED.  The reference's WSHandler.cpp cannot be compiled in this
- * image without writing stand-ins for the absent libkev headers
- * (third_party/libkev is an empty submodule), which this build does not do,
- * and the reference's own tests hold no WebSocket vectors (unittest/ covers
- * KMBuffer and Base64 only).  So no reference-held or reference-run fixture
- * checks this restatement.  What checks it (tests/golden/reference_vectors.json):
- * the RFC 6455 sec.5.7 known-answer frames -- independent of kuma, they pin the
- * protocol-defined parts (masking, the three length classes, fragmentation) --
- * and values transcribed from SURVEY.md sec.8 (a-2, a-4, a-5 tables, from a
- * survey-session build of WSHandler.cpp that needed stand-in headers: a record,
- * not a pin).  See DESIGN.md sec.2 "Oracle".
+ * PINNED to the reference's own compiled code.  oracle/ref_build.py compiles the
+ * reference's unmodified WSHandler.cpp (stand-ins for the absent libkev headers
+ * in oracle/ref_shim/, the wrapper oracle/ref_wrap.cpp with this file's ABI under
+ * a ref_ prefix) at -O3 and -O0, and tests/test_oracle_vs_reference.py compares
+ * orc_mask, orc_encode_header and the orc_decoder_* functions with it on every
+ * observable: return codes, callbacks, all header fields, the caller's buffer.
+ * tests/golden/reference_recorded.json holds outputs recorded from that build
+ * and checks this file where the reference is absent; reference_vectors.json
+ * adds the RFC 6455 sec.5.7 known answers.  The batch helpers at the end are
+ * loops over pinned functions; sendWsFrame's composition (orc_encode_batch)
+ * stays a restatement.  See DESIGN.md sec.2 "Oracle".
  */
 #include <stdint.h>
 #include <stdlib.h>

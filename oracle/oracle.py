@@ -1,7 +1,9 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes wrapper over oracle/kmws_oracle.c.
 
 The CPU restatement of kuma's src/ws codec (see the header of kmws_oracle.c
-for the reference lines each function restates and for how it is pinned).
+for the reference lines each function restates and for how it is pinned), and
+`reference(opt)`: the same surface over kuma's own compiled WSHandler.cpp
+(oracle/ref_build.py), the code the restatement is pinned to.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import
 this module, and only as the checker / the timed CPU baseline; the product
 (kuma_amd/) never does.
@@ -148,7 +150,7 @@ class Decoder:
     """WSHandler streaming decoder (WSHandler.cpp:108-280) over the C oracle."""
 
     def __init__(self, mode: int = SERVER):
-        self._d = lib().orc_decoder_create(mode)
+        self._d = self._create(mode)
         self.frames: List[Frame] = []
         self.destroy_on: Optional[int] = None  # emulate callback destroying handler at frame k
 
@@ -162,6 +164,12 @@ class Decoder:
             return 0
 
         self._cb = FRAME_CB(_cb)
+
+    def _create(self, mode):
+        return lib().orc_decoder_create(mode)
+
+    def _feed(self, buf, n):
+        return lib().orc_decoder_feed(self._d, buf, n, self._cb, None)
 
     def __del__(self):
         try:
@@ -178,7 +186,7 @@ class Decoder:
             buf = (C.c_uint8 * len(data)).from_buffer(data)
         else:
             buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
-        return lib().orc_decoder_feed(self._d, buf, len(data), self._cb, None)
+        return self._feed(buf, len(data))
 
     def reset(self) -> None:
         lib().orc_decoder_reset(self._d)
@@ -191,9 +199,9 @@ class Decoder:
         return lib().orc_decoder_state(self._d)
 
 
-def decode_chunks(stream: bytes, mode: int, chunk: int) -> Tuple[List[int], List[Frame]]:
+def decode_chunks(stream: bytes, mode: int, chunk: int, decoder=None) -> Tuple[List[int], List[Frame]]:
     """Feed `stream` in chunks of `chunk` bytes (0 = whole) and collect results."""
-    d = Decoder(mode)
+    d = (decoder or Decoder)(mode)
     rets = []
     if chunk <= 0:
         rets.append(d.feed(stream))
@@ -254,3 +262,115 @@ def encode_batch(src: np.ndarray, src_off: np.ndarray, lens: np.ndarray, flags: 
     lib().orc_encode_batch(_ptr(src), _ptr(src_off), _ptr(lens), _ptr(flags), _ptr(keys),
                            n, _ptr(dst), _ptr(wire_off))
     return dst[:int(total)], wire_off
+
+
+# ---------------------------------------------------------------------------
+# The built reference (oracle/ref_build.py): kuma's own compiled WSHandler.cpp
+# behind oracle/ref_wrap.cpp, the same surface as the functions above.
+class Reference:
+    """Backend over oracle/_ref/libkmws_ref_<opt>.so: `Decoder`,
+    `encode_header`, `mask`, `mask_bytes`, `mask_chain` and `decode_chunks` as
+    this module has them, run by the reference's compiled code.  There is no
+    `Decoder.state` (WSHandler has no accessor), and a feed after the callback
+    destroyed the handler returns DESTROYED without reaching the reference."""
+
+    def __init__(self, path: str, opt: str):
+        self.opt, self.path = opt, path
+        L = self._lib = C.CDLL(path)
+        L.ref_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        L.ref_mask_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ref_encode_header.argtypes = [C.POINTER(OrcHdr), C.c_void_p]
+        L.ref_encode_header.restype = C.c_int
+        L.ref_decoder_create.argtypes = [C.c_int]
+        L.ref_decoder_create.restype = C.c_void_p
+        L.ref_decoder_destroy.argtypes = [C.c_void_p]
+        L.ref_decoder_reset.argtypes = [C.c_void_p]
+        L.ref_decoder_set_mode.argtypes = [C.c_void_p, C.c_int]
+        L.ref_decoder_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, FRAME_CB, C.c_void_p]
+        L.ref_decoder_feed.restype = C.c_int
+
+        class RefDecoder(Decoder):
+            """WSHandler itself (handleData, reset, setMode, the frame callback)."""
+
+            def _create(self, mode):
+                return L.ref_decoder_create(mode)
+
+            def __del__(self):
+                try:
+                    if self._d:
+                        L.ref_decoder_destroy(self._d)
+                        self._d = None
+                except Exception:
+                    pass
+
+            def _feed(self, buf, n):
+                return L.ref_decoder_feed(self._d, buf, n, self._cb, None)
+
+            def reset(self) -> None:
+                L.ref_decoder_reset(self._d)
+
+            def set_mode(self, mode: int) -> None:
+                L.ref_decoder_set_mode(self._d, mode)
+
+            @property
+            def state(self) -> int:
+                raise AttributeError("the reference has no decode-state accessor")
+
+        RefDecoder.__name__ = f"RefDecoder_{opt}"
+        self.Decoder = RefDecoder
+
+    def __repr__(self):
+        return f"Reference({self.opt})"
+
+    def mask(self, key: bytes, data, phase: int = 0) -> None:
+        k = (C.c_uint8 * 4).from_buffer_copy(bytes(key))
+        if isinstance(data, np.ndarray):
+            self._lib.ref_mask(k, _ptr(data), data.nbytes, phase)
+        else:
+            buf = (C.c_uint8 * len(data)).from_buffer(data)
+            self._lib.ref_mask(k, buf, len(data), phase)
+
+    def mask_bytes(self, key: bytes, data: bytes, phase: int = 0) -> bytes:
+        b = bytearray(data)
+        if b:
+            self.mask(key, b, phase)
+        return bytes(b)
+
+    def mask_chain(self, key: bytes, segments: Sequence[bytes]) -> List[bytes]:
+        """One KMBuffer chain with a segment per entry, empty ones included,
+        through handleDataMask(key, KMBuffer&) (WSHandler.cpp:312-322)."""
+        n = len(segments)
+        if n == 0:
+            return []
+        k = (C.c_uint8 * 4).from_buffer_copy(bytes(key))
+        bufs = [(C.c_uint8 * max(1, len(s))).from_buffer_copy(bytes(s) or b"\0") for s in segments]
+        ptrs = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+        lens = (C.c_size_t * n)(*[len(s) for s in segments])
+        self._lib.ref_mask_chain(k, ptrs, lens, n)
+        return [bytes(b[:len(s)]) for b, s in zip(bufs, segments)]
+
+    def encode_header(self, h: Hdr) -> bytes:
+        c = OrcHdr()
+        c.fin, c.rsv1, c.rsv2, c.rsv3 = h.fin, h.rsv1, h.rsv2, h.rsv3
+        c.opcode, c.mask, c.length = h.opcode, h.mask, h.length & 0xFFFFFFFF
+        for i in range(4):
+            c.maskey[i] = h.maskey[i]
+        out = (C.c_uint8 * 14)()
+        n = self._lib.ref_encode_header(C.byref(c), out)
+        return bytes(out[:n])
+
+    def decode_chunks(self, stream: bytes, mode: int, chunk: int) -> Tuple[List[int], List[Frame]]:
+        return decode_chunks(stream, mode, chunk, decoder=self.Decoder)
+
+
+_refs: dict = {}
+
+
+def reference(opt: str = "O3") -> Optional[Reference]:
+    """The backend over the built reference at optimisation level `opt`
+    ("O3" or "O0"), or None where oracle/_ref/ does not hold that library."""
+    if opt not in _refs:
+        from oracle import ref_build
+        path = ref_build.lib_path(opt)
+        _refs[opt] = Reference(path, opt) if os.path.exists(path) else None
+    return _refs[opt]

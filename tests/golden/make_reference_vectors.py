@@ -1,4 +1,17 @@
-"""Writes tests/golden/reference_vectors.json.
+"""Writes tests/golden/reference_vectors.json (no argument) or records
+tests/golden/reference_recorded.json from the built reference (--record).
+
+--record: every case of reference_vectors.json again, the streaming-state
+cases, the encode table and the mask table of tests/ref_cases.py, each run
+through oracle/_ref/libkmws_ref_O3.so -- kuma's own WSHandler.cpp as
+oracle/ref_build.py compiles it -- and written with what that library
+returned: same schema, plus "recorded_from" and the schema extensions
+tests/ref_cases.py lists.  Nothing of it is transcribed and nothing comes from
+the oracle.  tests/test_oracle_golden.py runs the oracle over the file
+everywhere and, where the reference is built, records again in memory and
+compares, so a stale file fails.
+
+The rest of this text is about reference_vectors.json.
 
 Every expected value below is TRANSCRIBED, not computed: each case cites where
 its expected output was observed --
@@ -6,11 +19,11 @@ its expected output was observed --
   * "SURVEY-a-N": an output of the reference's own src/ws/WSHandler.cpp, run
     in the survey container and recorded in SURVEY.md section 8 (row a-N).
 Nothing here imports or runs the oracle or the product, so the JSON checks the
-oracle (tests/test_oracle_golden.py) instead of echoing it.  By the task's rules
-only the RFC cases are independent known answers: the SURVEY cases were recorded
-from a build of WSHandler.cpp that needed stand-in libkev headers and that no
-committed recipe reproduces, so they record the reference's behaviour without
-pinning it -- parity is "unpinned" (DESIGN.md sec.2).
+oracle (tests/test_oracle_golden.py) instead of echoing it.  The RFC cases are
+independent known answers; the SURVEY cases were written down from a survey
+session's build of WSHandler.cpp.  The pin is the recorded file: every case here
+is recorded again there, and tests/test_oracle_golden.py asserts that the
+transcribed values equal the recorded ones.
 
 Large payloads are described by a generator name + length instead of bytes:
   "zeros"  -> b"\\0" * n,   "iota" -> bytes(i & 0xFF for i in range(n)).
@@ -142,7 +155,66 @@ out = dict(
            "see make_reference_vectors.py."),
     decode=decode, encode=encode, mask=mask)
 
-path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_vectors.json")
-with open(path, "w") as f:
-    json.dump(out, f, indent=1)
-print("wrote", path, len(decode), "decode,", len(encode), "encode,", len(mask), "mask cases")
+HERE = os.path.dirname(os.path.abspath(__file__))
+RECORDED_FROM = "libkmws_ref_O3"
+
+
+def recorded(backend):
+    """The content of reference_recorded.json as `backend` gives it."""
+    import sys
+    tests_dir = os.path.dirname(HERE)
+    for p in (tests_dir, os.path.dirname(tests_dir)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import ref_cases as rc
+
+    dec = [rc.record_decode(backend, c) for c in decode + rc.streaming_cases()]
+    enc = [dict(c) for c in encode] + [rc.encode_case(*row) for row in rc.encode_table_fixture()]
+    for c in enc:
+        c["expect_hex"] = rc.encode_run(backend, c)
+    msk = [dict(c) for c in mask] + [rc.mask_case(*row) for row in rc.mask_table_fixture()]
+    for c in msk:
+        c["expect_hex"] = rc.mask_run(backend, c)
+    return dict(
+        about=("Outputs of kuma's own src/ws/WSHandler.cpp, compiled by oracle/ref_build.py and run "
+               "by make_reference_vectors.py --record. Recorded, not transcribed."),
+        recorded_from=RECORDED_FROM, decode=dec, encode=enc, mask=msk)
+
+
+def dumps_recorded(doc):
+    """One case per line: the file stays small and diffs stay readable."""
+    lines = ["{", ' "about": ' + json.dumps(doc["about"]) + ",",
+             ' "recorded_from": ' + json.dumps(doc["recorded_from"]) + ","]
+    for i, sect in enumerate(("decode", "encode", "mask")):
+        lines.append(f' "{sect}": [')
+        rows = [json.dumps(c, separators=(",", ":")) for c in doc[sect]]
+        lines += ["  " + r + ("," if k + 1 < len(rows) else "") for k, r in enumerate(rows)]
+        lines.append(" ]" + ("," if i < 2 else ""))
+    lines.append("}")
+    return "\n".join(lines) + "\n"
+
+
+def main(argv):
+    if "--record" in argv:
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+        from oracle import oracle as orc
+        ref = orc.reference("O3")
+        if ref is None:
+            raise SystemExit("oracle/_ref/libkmws_ref_O3.so is not built (run oracle/ref_build.py)")
+        doc = recorded(ref)
+        path = os.path.join(HERE, "reference_recorded.json")
+        with open(path, "w") as f:
+            f.write(dumps_recorded(doc))
+        print("recorded", path, len(doc["decode"]), "decode,", len(doc["encode"]), "encode,",
+              len(doc["mask"]), "mask cases")
+        return
+    path = os.path.join(HERE, "reference_vectors.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", path, len(decode), "decode,", len(encode), "encode,", len(mask), "mask cases")
+
+
+if __name__ == "__main__":
+    import sys
+    main(sys.argv[1:])

@@ -220,14 +220,15 @@ def _piece(wire, a, b):
     return bytearray(wire[a:b])
 
 
-def expect_full(wire, wire_len, hdr_off, f, mode):
+def expect_full(wire, wire_len, hdr_off, f, mode, decoder=orc.Decoder):
     """(err, off, len, key, flags, payload): the contract of kmws_unpack_headers
-    for frame f, from the oracle decoder alone (payload: the oracle's unmasked
-    bytes of a good frame, else b"")."""
+    for frame f, from the decoder alone (payload: its unmasked bytes of a good
+    frame, else b"").  decoder: the oracle's Decoder class, or the built
+    reference's (oracle.reference().Decoder)."""
     h = int(hdr_off[f])
     nxt = int(hdr_off[f + 1]) if f + 1 < len(hdr_off) else int(wire_len)
     flags = (int(wire[h]) | ((int(wire[h + 1]) >> 7) << 8)) if h + 2 <= wire_len else 0
-    d = orc.Decoder(mode)
+    d = decoder(mode)
     d.destroy_on = 0  # stop at the first delivered frame
     # the bytes from h to the wire's end, fed to one decoder in pieces: up to the
     # next header first, more only while it asks for more
@@ -248,18 +249,18 @@ def expect_full(wire, wire_len, hdr_off, f, mode):
         return ret, h, 0, 0, flags, b""
     if ret in (0, 1):
         return 1, h, 0, 0, flags, b""
-    raise AssertionError(f"oracle returned {ret} for the frame at {h}")
+    raise AssertionError(f"{decoder.__name__} returned {ret} for the frame at {h}")
 
 
-def expect(wire, wire_len, hdr_off, f, mode):
+def expect(wire, wire_len, hdr_off, f, mode, decoder=orc.Decoder):
     """(err, off, len, key, flags) of frame f: see expect_full."""
-    return expect_full(wire, wire_len, hdr_off, f, mode)[:5]
+    return expect_full(wire, wire_len, hdr_off, f, mode, decoder)[:5]
 
 
 class Expected:
     """expect over a whole batch as arrays, and the good frames' payloads."""
 
-    def __init__(self, wire, wire_len, hdr_off, mode):
+    def __init__(self, wire, wire_len, hdr_off, mode, decoder=orc.Decoder):
         n = len(hdr_off)
         self.err = np.zeros(n, np.uint8)
         self.off = np.zeros(n, np.int64)
@@ -269,7 +270,7 @@ class Expected:
         self.payload = [b""] * n
         for f in range(n):
             (self.err[f], self.off[f], self.len[f], self.key[f], self.flags[f],
-             self.payload[f]) = expect_full(wire, wire_len, hdr_off, f, mode)
+             self.payload[f]) = expect_full(wire, wire_len, hdr_off, f, mode, decoder)
 
     def desc(self):
         """(n, 2) int64 as the device writes kmws_desc: off, len | key << 32."""
@@ -283,13 +284,13 @@ def corpus_expected(mode):
 
 
 # ------------------------------ walk model and streams ------------------------------
-def walk_expect(stream, cap):
+def walk_expect(stream, cap, decoder=orc.Decoder):
     """(offsets, consumed) the header-chain walks must give for one stream: the
     offsets of the frames a SERVER oracle delivers, one more if bytes remain,
     the oracle did not close and fewer than cap are recorded; consumed = the end
     of the last delivered frame among those recorded."""
     stream = bytes(stream)
-    d = orc.Decoder(SERVER)
+    d = decoder(SERVER)
     ret = d.feed(stream) if stream else 0
     offs, ends, p = [], [], 0
     for fr in d.frames:
