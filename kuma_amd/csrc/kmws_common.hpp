@@ -244,7 +244,6 @@ constexpr int kResMaxDescs = KMWS_RESIDENT_MAX_PAYLOADS;
 // the pieces kernel alone ~20 us.  Synchronous (a flush, a feed, a mask) and
 // asynchronous jobs (an rx / tx batch's submit) alike.
 constexpr uint64_t kResMaxBytes = KMWS_RESIDENT_MAX_BYTES;
-constexpr uint64_t kResMaxBytesAsync = kResMaxBytes;
 // A checked job (kmws_decoder_set_utf8_check) above this many bytes launches:
 // the grid validates with the 16 waves of one workgroup per part, four to a
 // SIMD, and the rule's ALU work no longer hides behind PCIe as it does in a

@@ -193,7 +193,7 @@ struct GenQueue {
     // launches and waits -- and then either rotates or restores.
     kmws_status launch(bool sync)
     {
-        const kmws_status st = sync ? stage->run(ring) : stage->launch(ring, kResMaxBytesAsync);
+        const kmws_status st = sync ? stage->run(ring) : stage->launch(ring, kResMaxBytes);
         ring.list.clear();
         return st;
     }

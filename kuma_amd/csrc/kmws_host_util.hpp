@@ -303,7 +303,7 @@ public:
     // staged or extra, is posted with its views and the zeroed verdict bytes if
     // it has at most min(max_res_bytes, kResMaxBytesChecked) bytes, else
     // launches the pieces kernel with the check.
-    kmws_status launch(const ExtraBuf& extra = ExtraBuf(), uint64_t max_res_bytes = kResMaxBytesAsync)
+    kmws_status launch(const ExtraBuf& extra = ExtraBuf(), uint64_t max_res_bytes = kResMaxBytes)
     {
         const std::vector<kmws_desc>& d2 = extra.list.descs;
         const std::vector<Utf8View>& v2 = extra.list.views;

@@ -45,11 +45,10 @@
 #include "kmws_bench.h"
 #include "kmws_host_util.hpp"
 #include "kmws_utf8_dev.hpp"
+#include "kmws_resident_proto.hpp"
 
 namespace kmws {
 
-constexpr int kResBlock = 1024;  // 16 waves: 4 words each = 64 KiB of loads in flight
-constexpr int kResWords = 4;
 // Jobs of up to this many 16-byte words store write-through (sc0 sc1) and end
 // without a release; larger ones store into the L2 and end with one
 // system-scope release (a buffer_wbl2 of the XCD's L2) -- unless a device
@@ -60,17 +59,6 @@ constexpr int kResWords = 4;
 // through stores of 64 KiB generations halved 8 loopback connections' decode
 // (18.6 -> 8.6-10.9 GiB/s, r06an-ap).  The thread decides (kWriteThroughBit).
 constexpr int kResWriteThroughWords = 1024;
-// Slots per device: one per loop thread that uses the synchronous entries
-// (kuma's test client runs 10 loop threads, its server 5).  Unclaimed slots'
-// workgroups poll one word every few microseconds; a claimed slot's workgroup
-// polls its job word and 31 descriptor slots (512 B) back to back.
-constexpr int kResSlots = 16;
-// Workgroups per slot: one CU moves ~13 GB/s of a job's PCIe traffic (the misses
-// it keeps in flight to host memory bound it, not its lanes), so a job of at
-// least 2 x kPartWords words is split over up to kResParts workgroups, each
-// polling the slot's job word itself.
-constexpr int kResParts = 4;
-constexpr uint32_t kPartWords = 1024;  // 16 KiB: the least a part takes
 // Idle exit: short.  The runtime maps streams onto a few hardware queues
 // (GPU_MAX_HW_QUEUES, 4 on the box), so a kernel launched on a stream that
 // shares the worker's queue waits until the worker leaves; and
@@ -111,12 +99,6 @@ static inline void cpu_relax()
 #endif
 }
 
-struct ResDesc {  // one payload: device-visible address, bytes, LE key of its first byte
-    uint64_t addr;
-    uint32_t len;
-    uint32_t key;
-};
-static_assert(sizeof(ResDesc) == 16, "ResDesc is one 16-byte load");
 // What a checked job adds (ResSlot::view, ::verdict): per payload its view
 // word and its host address (the edge words are read there), and the device
 // view of the verdict bytes.
@@ -124,102 +106,6 @@ struct ResCheckArgs {
     uint64_t view[kResMaxDescs];
     const uint8_t* host[kResMaxDescs];
     uint64_t verdict;
-};
-
-// The polled word of a slot: job number (bits 0-39), payload count (40-47),
-// parts - 1 (48-49: the workgroups the job is split over), cancelled (61: a
-// job its thread withdrew -- no workgroup runs it), claimed (62: a thread holds
-// the slot, so its part-0 workgroup polls the descriptors too) and quit (63).
-// The first kPollDescs descriptor slots follow it and are read with it at
-// every poll of part 0, so a job of up to kPollDescs payloads costs one PCIe
-// round trip to notice and none more to read its descriptors.  The host
-// rewrites every one of those slots for every job (unused ones with length 0),
-// each as two 8-byte stores tagged with the job's low bits (address bits
-// 48-63; length bits 21-31 in the half that also holds the key): a half read
-// before the host's write landed carries the previous job's tag, and the job's
-// descriptors are then read again after the word.
-constexpr uint64_t kJobMask = (1ull << 40) - 1;
-constexpr int kPartShift = 48;
-constexpr uint64_t kWriteThroughBit = 1ull << 50;  // the job's stores write through (no release)
-// A checked job (kmws_decoder_set_utf8_check): its text payloads are validated
-// in the pass that unmasks them.  Only the validating instantiation of the
-// kernel takes one (ResidentWorker::post); the slot's view words, edge words
-// and the verdict word beside the job word belong to it (ResSlot).
-constexpr uint64_t kCheckBit = 1ull << 51;
-constexpr uint64_t kCancelBit = 1ull << 61;
-constexpr uint64_t kClaimedBit = 1ull << 62;
-constexpr uint64_t kQuitBit = 1ull << 63;
-// word + 31 slots: a slot's first 512 bytes, one 16-byte load per lane of
-// wave 0 -- a cfg1 read (16 frames of 4 KiB, and a partial one) fits
-constexpr int kPollDescs = 31;
-static_assert(kPollDescs < 64, "one lane of wave 0 per polled slot");
-constexpr uint64_t kAddrMask = (1ull << 48) - 1;
-constexpr uint32_t kLenMask = (1u << 21) - 1;  // kResMaxBytes fits
-static_assert(kResMaxBytes <= kLenMask && kResMaxBytesAsync <= kLenMask, "tagged length");
-__host__ __device__ __forceinline__ ResDesc tag_desc(ResDesc x, uint64_t job)
-{
-    x.addr |= (job & 0xFFFFull) << 48;
-    x.len |= (uint32_t)(job & 0x7FFu) << 21;
-    return x;
-}
-__host__ __device__ __forceinline__ bool desc_tagged(const ResDesc& x, uint64_t job)
-{
-    return (x.addr >> 48) == (job & 0xFFFFull) && (x.len >> 21) == (uint32_t)(job & 0x7FFu);
-}
-__host__ __device__ __forceinline__ ResDesc untag_desc(ResDesc x)
-{
-    x.addr &= kAddrMask;
-    x.len &= kLenMask;
-    return x;
-}
-// Words of a payload's 16-byte aligned hull.
-__host__ __device__ __forceinline__ uint32_t hull_words(uint64_t addr, uint32_t len)
-{
-    return len ? (uint32_t)(((addr + len + 15) >> 4) - (addr >> 4)) : 0u;
-}
-
-// Pinned host memory.  Host-written and device-written words sit in different
-// 128-byte lines.
-struct alignas(256) ResSlot {
-    uint64_t word;  // job | ndesc << 40 | (parts - 1) << 48 | cancel << 61 | claimed << 62 | quit << 63
-    // A checked job: the device view of its stage's verdict bytes, tagged with
-    // the job's low 16 bits in bits 48-63 like a descriptor's address.  It
-    // arrives with lane 0's poll of the job word; a stale tag is read again
-    // after the word.
-    uint64_t verdict;
-    ResDesc desc[kResMaxDescs];  // desc[i] at 16 + 16 i
-    // A checked job, written by the host before the job word and read after it
-    // was seen, together with the first payload loads (no round trip of their
-    // own).  view[i]: Utf8View::w of payload i (look-back bits 0-23,
-    // kUtf8Checked) | the index of its verdict byte << 32.  edge[p]: the four
-    // bytes before part p's first word as they lay in host memory before the
-    // post, still masked -- part p - 1 may have stored them unmasked by the time
-    // part p runs (PieceRecEdge::edge of the launched kernel); unused where
-    // the part starts on a payload's first word, which takes the view.
-    uint64_t view[kResMaxDescs];
-    uint64_t edge[kResParts];
-    alignas(128) uint64_t done[kResParts];  // per part: last job number finished (release: its bytes visible)
-    uint64_t gone[kResParts];               // per part: incarnation whose workgroup has left
-    alignas(128) uint64_t pad2;
-};
-struct ResMailbox {
-    ResSlot slot[kResSlots];
-    alignas(128) uint64_t exited;  // incarnation whose last workgroup has left (device)
-    alignas(128) uint64_t resize;  // (host) incarnations up to this one leave: a slot was claimed outside them
-    alignas(128) uint64_t pad3;
-};
-// Why a workgroup left: its lease ran out, another workgroup found the grid
-// idle (closing), a thread asked for a resize, it found the grid idle itself,
-// its slot's quit bit.
-constexpr int kResExitReasons = 5;
-// Device memory, shared by the grid's workgroups.  Counters and marks are
-// compared with the incarnation number, so nothing is cleared between launches.
-struct ResCtl {
-    uint64_t closing;   // max incarnation that is leaving (idle or lease)
-    uint64_t exits;     // workgroups exited, all incarnations (each adds the grid size)
-    uint64_t idle;      // workgroups of the running incarnation idle 200 us (or gone on their quit bit)
-    uint64_t pad;
-    uint64_t why[kResExitReasons];  // workgroup exits by reason (kmws_resident_exit_reasons)
 };
 
 // Loads of host-written words bypass every cache (and are never scalar loads).
@@ -265,6 +151,28 @@ __device__ __forceinline__ uint64_t ld_agent(const uint64_t* p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Lane 0's value in every lane (each half through uint32_t: readfirstlane is signed).
+__device__ __forceinline__ uint64_t first_lane64(uint64_t v)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
+}
+// One descriptor of the slot, read after the job word was seen.
+__device__ __forceinline__ ResDesc load_desc(const ResDesc* d)
+{
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(d);
+    const uint64_t lo = ld_sys(q), hi = ld_sys(q + 1);  // each half one 8-byte load
+    return untag_desc(ResDesc{lo, (uint32_t)hi, (uint32_t)(hi >> 32)});
+}
+// Wave 0's state from poll to poll.  (The order of the fields is the one that
+// keeps the kernel's registers where they were: profiles/p12_resident_isa.txt.)
+struct Wave0 {
+    bool full;       // poll the descriptors too
+    bool idle;       // counted in ctl->idle
+    uint64_t last;   // job seen last
+    uint64_t t_act;  // this slot's latest job
+    uint32_t why;    // the exit reason (ResCtl::why, ResExit)
+};
 
 // nslots x kResParts workgroups (slots 0 .. nslots - 1: those claimed when
 // the incarnation was launched), persistent until idle: workgroup blockIdx.x
@@ -324,18 +232,15 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
     // a device-wide "last job" time other workgroups wrote, and under load read
     // it stale or skewed: 16 busy threads' grids closed as idle every ~0.3 ms
     // (r05as / r05at: 650-1,199 idle decisions in 25 ms; 1.26 M calls/s).
-    uint64_t last = 0, t_act = born;  // (wave 0) job seen last; this slot's latest job
-    bool idle = false;                // (wave 0) counted in ctl->idle
-    bool full = part == 0;            // (wave 0) poll the descriptors too
-    uint32_t why = 0;                 // (wave 0) the exit reason (ResCtl::why)
-    if (t < 64) last = ld_sys(&sl->done[part]);
+    Wave0 s{part == 0, false, 0, born, kExitLease};
+    if (t < 64) s.last = ld_sys(&sl->done[part]);
     for (;;) {
         if (t < 64) {  // wave 0, uniform control flow
             uint64_t cmd = 0, v0 = 0, v1 = 0;
             bool polled_full = false;
             for (uint32_t it = 0;; ++it) {
                 const uint64_t now = wall_clock64();
-                const uint64_t* a = full ? pw : pw0;
+                const uint64_t* a = s.full ? pw : pw0;
                 v0 = ld_sys(a);
                 v1 = ld_sys(a + 1);
                 // with the word's loads in flight: is the grid leaving (idle;
@@ -348,43 +253,41 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                 if ((it & 3u) == 0) closing = ld_agent(&ctl->closing);
                 if ((it & 15u) == 0) resize = ld_sys(&mb->resize);
                 if ((uint64_t)(now - born) > lease_ticks || closing >= inc || resize >= inc) {
-                    why = closing >= inc ? 1u : resize >= inc ? 2u : 0u;
+                    s.why = closing >= inc ? kExitClosing : resize >= inc ? kExitResize : kExitLease;
                     cmd = 0;
                     break;
                 }
-                polled_full = full;
-                const uint64_t w = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v0) |
-                                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v0 >> 32)) << 32;
-                // (lane 0's job word; each half through uint32_t: readfirstlane is signed)
-                if (w & kQuitBit) {  // this slot only: the rest of the grid serves on
-                    why = 4;
+                polled_full = s.full;
+                const uint64_t w = first_lane64(v0);  // lane 0's job word
+                if (job_quit(w)) {  // this slot only: the rest of the grid serves on
+                    s.why = kExitQuit;
                     break;
                 }
-                if ((w & kJobMask) != last) {  // a job on this slot: activity, whichever part it is for
-                    t_act = now;
-                    if (idle) {
+                const uint64_t job = job_number(w);
+                if (job != s.last) {  // a job on this slot: activity, whichever part it is for
+                    s.t_act = now;
+                    if (s.idle) {
                         if (t == 0) __hip_atomic_fetch_sub(&ctl->idle, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        idle = false;
+                        s.idle = false;
                     }
-                    const uint32_t parts = (uint32_t)(w >> kPartShift & 3u) + 1u;
+                    const uint32_t parts = job_parts(w);
                     if (part >= parts || (w & kCancelBit)) {
-                        last = w & kJobMask;  // not this workgroup's (no done word: nobody waits for it)
+                        s.last = job;  // not this workgroup's (no done word: nobody waits for it)
                         continue;
                     }
                     cmd = w;
                     break;
                 }
-                const bool claimed = (w & kClaimedBit) != 0;
-                full = part == 0 && claimed;
-                if (!idle && (uint64_t)(now - t_act) > idle_ticks) {  // idle here: counted
+                const bool claimed = job_claimed(w) != 0;
+                s.full = part == 0 && claimed;
+                if (!s.idle && (uint64_t)(now - s.t_act) > idle_ticks) {  // idle here: counted
                     uint64_t before = 0;
                     if (t == 0) before = __hip_atomic_fetch_add(&ctl->idle, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    before = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)before) |
-                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(before >> 32)) << 32;
-                    idle = true;
+                    before = first_lane64(before);
+                    s.idle = true;
                     if (before + 1 >= gridDim.x) {  // every workgroup idle: the grid leaves
                         if (t == 0) __hip_atomic_fetch_max(&ctl->closing, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        why = 3;
+                        s.why = kExitIdle;
                         break;
                     }
                 }
@@ -393,10 +296,10 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
             }
             uint32_t have = 0;
             if (cmd) {
-                const uint32_t nd = (uint32_t)(cmd >> 40) & 0xFFu;
+                const uint32_t nd = job_count(cmd);
                 const ResDesc x = ResDesc{v0, (uint32_t)v1, (uint32_t)(v1 >> 32)};
                 const bool mine = polled_full && t >= 1 && t <= (int)nd && t <= kPollDescs;
-                const bool ok = desc_tagged(x, cmd & kJobMask);
+                const bool ok = desc_tagged(x, job_number(cmd));
                 if (mine && ok) s_d[t - 1] = untag_desc(x);
                 // every descriptor of the job came with the word: no second round trip
                 const uint64_t bad = __ballot(mine && !ok);
@@ -408,9 +311,9 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                 if constexpr (kCheck) {
                     // lane 0's second half is the word beside the job word: the
                     // verdict bytes' address, read again if its tag is stale
-                    if (t == 0 && (cmd & kCheckBit)) {
-                        if ((v1 >> 48) != (cmd & 0xFFFFull)) v1 = ld_sys(pw0 + 1);
-                        s_verdict = v1 & kAddrMask;
+                    if (t == 0 && job_checked(cmd)) {
+                        if (!verdict_tagged(v1, cmd)) v1 = ld_sys(pw0 + 1);
+                        s_verdict = untag_verdict(v1);
                     }
                 }
             }
@@ -422,14 +325,9 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
         __syncthreads();
         const uint64_t cmd = s_cmd;
         if (cmd == 0) break;  // every wave leaves together
-        const uint32_t nd = (uint32_t)(cmd >> 40) & 0xFFu;
+        const uint32_t nd = job_count(cmd);
         const uint32_t n = nd < (uint32_t)kResMaxDescs ? nd : (uint32_t)kResMaxDescs;
-        const uint32_t parts = (uint32_t)(cmd >> kPartShift & 3u) + 1u;
-        if (s_have == 0 && t < (int)n) {
-            const uint64_t* q = reinterpret_cast<const uint64_t*>(&sl->desc[t]);
-            const uint64_t lo = ld_sys(q), hi = ld_sys(q + 1);  // each half one 8-byte load
-            s_d[t] = untag_desc(ResDesc{lo, (uint32_t)hi, (uint32_t)(hi >> 32)});
-        }
+        if (s_have == 0 && t < (int)n) s_d[t] = load_desc(&sl->desc[t]);
         __syncthreads();
 #ifdef KMWS_TEST_RESIDENT_STALL_KEY
         // test build only (kuma_amd/build.py): a job whose first payload's key
@@ -441,7 +339,7 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
             if (t == 0 && (ld_sys(pw0) & kQuitBit)) s_cmd = 0;
             __syncthreads();
             if (s_cmd == 0) {
-                why = 4;  // gone on its quit bit
+                s.why = kExitQuit;  // gone on its quit bit
                 break;
             }
         }
@@ -455,13 +353,12 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
             s_pre[n] = w;
         }
         __syncthreads();
-        const uint32_t total = s_pre[n];
-        const bool wt = (cmd & kWriteThroughBit) != 0;
-        // this part's words: an even share, in job order
-        const uint32_t wb = (uint32_t)((uint64_t)total * part / parts), we = (uint32_t)((uint64_t)total * (part + 1) / parts);
+        const bool wt = job_write_through(cmd) != 0;
+        const PartRange mine = part_range(s_pre[n], part, job_parts(cmd));  // this part's words
+        const uint32_t we = mine.end;
         // a checked part is one round with a barrier in it: every wave runs it
-        const bool chk = kCheck && (cmd & kCheckBit) != 0;
-        for (uint32_t w0 = wb; w0 < we; w0 += kResBlock * kResWords) {
+        const bool chk = kCheck && job_checked(cmd) != 0;
+        for (uint32_t w0 = mine.begin; w0 < we; w0 += kResBlock * kResWords) {
             if (!chk && w0 + (uint32_t)(t & ~63) >= we) break;  // nothing left for this wave (uniform)
             u32x4 v[kResWords];
             uint32_t di[kResWords];
@@ -491,7 +388,7 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                 di[i] = lo;
                 const ResDesc x = s_d[lo];
                 v[i] = u32x4{0, 0, 0, 0};
-                if (w < we) v[i] = *reinterpret_cast<const u32x4*>(((x.addr >> 4) + (w - s_pre[lo])) << 4);
+                if (w < we) v[i] = *reinterpret_cast<const u32x4*>(word_addr(x, w, s_pre[lo]));
             }
             // each word XORed with its payload's rotated key (the loads' registers
             // free from here: fewer live VGPRs leave more of each SIMD to a device
@@ -504,7 +401,7 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
             for (int i = 0; i < kResWords; ++i) {
                 const uint32_t w = w0 + t + kResBlock * i;
                 const ResDesc x = s_d[di[i]];
-                const uint64_t a = ((x.addr >> 4) + (w - s_pre[di[i]])) << 4;
+                const uint64_t a = word_addr(x, w, s_pre[di[i]]);
                 sv[i] = v[i] ^ rot_key(x.key, x.addr);
                 sa[i] = a;
                 // no short-circuit: with `&&` the compiler (ROCm 7.2, gfx950)
@@ -527,7 +424,7 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
             for (int i = 0; i < kResWords; ++i) {
                 if (!(edge >> i & 1u)) continue;
                 const ResDesc x = s_d[di[i]];
-                const uint64_t a = sa[i] == my_sink ? ((x.addr >> 4) + (w0 + t + kResBlock * i - s_pre[di[i]])) << 4 : sa[i];
+                const uint64_t a = sa[i] == my_sink ? word_addr(x, w0 + t + kResBlock * i, s_pre[di[i]]) : sa[i];
                 const uint64_t end = x.addr + x.len;
                 const uint64_t lo = a > x.addr ? a : x.addr, hi = a + 16 < end ? a + 16 : end;
                 for (uint64_t q = lo; q < hi; ++q) {
@@ -563,7 +460,7 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
                         if (lane == 0) prev = wave ? row[i][wave - 1] : (i ? row[i ? i - 1 : 0][kWaves - 1] : first);
                         const ResDesc x = s_d[di[i]];
                         const uint64_t view = s_view[di[i]];
-                        const uint64_t a = ((x.addr >> 4) + (w - s_pre[di[i]])) << 4;
+                        const uint64_t a = word_addr(x, w, s_pre[di[i]]);
                         bool bad = false;
                         if (w < we && (view & kUtf8Checked))
                             bad = plain_word_frame_bad(sv[i], prev, a, x.addr, x.addr + x.len, (uint32_t)view);
@@ -589,17 +486,17 @@ __global__ void __launch_bounds__(kResBlock) resident_unmask_kernel(ResMailbox* 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (t == 0) {
-            if (wt) __hip_atomic_store(&sl->done[part], cmd & kJobMask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            else __hip_atomic_store(&sl->done[part], cmd & kJobMask, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (wt) __hip_atomic_store(&sl->done[part], job_number(cmd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            else __hip_atomic_store(&sl->done[part], job_number(cmd), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (t < 64) {
-            last = cmd & kJobMask;
-            t_act = wall_clock64();  // the slot was busy until now (a long job is not idle time)
+            s.last = job_number(cmd);
+            s.t_act = wall_clock64();  // the slot was busy until now (a long job is not idle time)
         }
     }
     if (t == 0) {
-        __hip_atomic_fetch_add(&ctl->why[why < kResExitReasons ? why : 0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (why == 4 && !idle) {  // gone on its quit bit: idle for the rest of the incarnation
+        __hip_atomic_fetch_add(&ctl->why[s.why < kResExitReasons ? s.why : 0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (s.why == kExitQuit && !s.idle) {  // gone on its quit bit: idle for the rest of the incarnation
             const uint64_t b = __hip_atomic_fetch_add(&ctl->idle, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (b + 1 >= gridDim.x) __hip_atomic_fetch_max(&ctl->closing, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -622,13 +519,21 @@ T ld_acq(const T* p)
     return __atomic_load_n(p, __ATOMIC_ACQUIRE);
 }
 
-// Is job s of a slot finished, given the slot's done word?  Jobs of a slot run
-// one at a time in number order (40-bit, wrapping), so a done word at or past
-// s means s has run -- a ticket may be waited for after a later job of the
-// same slot finished.
-inline bool job_done(uint64_t done, uint64_t s) { return ((done - s) & kJobMask) < (1ull << 39); }
-
 using Clock = std::chrono::steady_clock;
+
+// A worker's event counts, behind the extern "C" counter entries: relaxed adds and reads.
+struct Counters {
+    // kUnownedPosts: posts refused, the caller did not hold the slot; kWtJobs, kReleasedJobs: jobs posted by
+    // kind (kWriteThroughBit); kLatePosts: jobs asked for after the thread gave its slots back (launched);
+    // kDrained: releases that first waited for the slot's last job
+    enum Id { kTimeouts, kWithdrawn, kUnownedPosts, kWtJobs, kReleasedJobs, kLatePosts, kDrained, kVariantSwitches, kCount };
+    void add(Id i) { __atomic_fetch_add(&v[i], 1, __ATOMIC_RELAXED); }
+    uint64_t get(Id i) const { return __atomic_load_n(&v[i], __ATOMIC_RELAXED); }
+    uint64_t v[kCount] = {};
+};
+// A part of a job: finished; not finished and its workgroup has left the grid
+// (nobody will run it there); or still held by a workgroup that may run it.
+enum class Part { kFinished, kLeft, kHeld };
 
 // One per device, shared by every host thread.  Slots are claimed with one
 // atomic on a bit mask; a job on a slot needs no lock (the slot's thread is
@@ -676,7 +581,7 @@ public:
         if (__atomic_load_n(&hs_[b].owner, __ATOMIC_ACQUIRE) != me) return true;  // not this thread's
         const uint64_t s = hs_[b].seq;
         if (s && hs_[b].cancelled != s && !all_done(mb_->slot[b], s, hs_[b].parts)) {
-            __atomic_fetch_add(&drained_, 1, __ATOMIC_RELAXED);
+            n_.add(Counters::kDrained);
             if (wait(b, s) == KMWS_ERR_TIMEOUT) return false;
         }
         __atomic_store_n(&hs_[b].owner, 0ull, __ATOMIC_RELEASE);
@@ -687,7 +592,7 @@ public:
     }
     // A thread whose slots were given back at its exit asked for a job: it
     // launches instead (counted).
-    void note_late_post() { __atomic_fetch_add(&late_posts_, 1, __ATOMIC_RELAXED); }
+    void note_late_post() { n_.add(Counters::kLatePosts); }
 
     // Ask every workgroup to leave at its next poll and wait for the grid (atexit).
     void quit_and_wait()
@@ -728,13 +633,13 @@ public:
     {
         if (n == 0 || n > (uint32_t)kResMaxDescs || !usable()) return KMWS_ERR_NOT_SUPPORTED;
         for (uint32_t i = 0; i < n; ++i)
-            if ((d[i].addr >> 48) != 0 || d[i].len > kLenMask) return KMWS_ERR_NOT_SUPPORTED;
-        if (ck && (ck->verdict >> 48) != 0) return KMWS_ERR_NOT_SUPPORTED;
+            if ((d[i].addr & ~kAddrMask) != 0 || d[i].len > kLenMask) return KMWS_ERR_NOT_SUPPORTED;
+        if (ck && (ck->verdict & ~kAddrMask) != 0) return KMWS_ERR_NOT_SUPPORTED;
         if (ck && !ld_acq(&checked_seen_)) __atomic_store_n(&checked_seen_, true, __ATOMIC_RELEASE);
         // only the slot's holder writes its descriptors and job word: a post
         // from any other thread is refused (and counted -- never expected)
         if (__atomic_load_n(&hs_[b].owner, __ATOMIC_ACQUIRE) != me) {
-            __atomic_fetch_add(&unowned_posts_, 1, __ATOMIC_RELAXED);
+            n_.add(Counters::kUnownedPosts);
             return KMWS_ERR_NOT_SUPPORTED;
         }
         ResSlot& sl = mb_->slot[b];
@@ -757,33 +662,25 @@ public:
         // the incarnation serving is the unchecked instantiation: it leaves as
         // for a resize, and the relaunch (the next post) is the validating one
         if (ck && !ld_acq(&inc_checked_)) {
-            if (__atomic_exchange_n(&switch_inc_, cur, __ATOMIC_ACQ_REL) != cur)
-                __atomic_fetch_add(&variant_switches_, 1, __ATOMIC_RELAXED);
+            if (__atomic_exchange_n(&switch_inc_, cur, __ATOMIC_ACQ_REL) != cur) n_.add(Counters::kVariantSwitches);
             request_resize(cur);
             return KMWS_ERR_NOT_SUPPORTED;
         }
         const uint64_t s = (prev + 1) & kJobMask;
         uint64_t words = 0;
         for (uint32_t i = 0; i < n; ++i) words += hull_words(d[i].addr, d[i].len);
-        const uint32_t parts = (uint32_t)std::min<uint64_t>(kResParts, std::max<uint64_t>(1, words / kPartWords));
-        // a checked part is one round of the kernel (no look-back is carried
-        // between rounds): at most kResBlock * kResWords words
-        if (ck && (words + parts - 1) / parts > (uint64_t)(kResBlock * kResWords)) return KMWS_ERR_NOT_SUPPORTED;
+        const uint32_t parts = part_count(words);
+        if (ck && !checked_fits(words, parts)) return KMWS_ERR_NOT_SUPPORTED;
         if (ck) {
             for (uint32_t i = 0; i < n; ++i) __atomic_store_n(&sl.view[i], ck->view[i], __ATOMIC_RELAXED);
             // the dword before each later part's first word, read before any
-            // workgroup can have stored it (the device splits at the same words)
+            // workgroup can have stored it (edge_pick: the device's own split)
             for (uint32_t p = 1; p < parts; ++p) {
-                const uint64_t wb = words * p / parts;
-                uint64_t pre = 0;
+                const EdgePick e = edge_pick(d, n, (uint32_t)words, p, parts);
                 uint32_t edge = 0;
-                for (uint32_t i = 0; i < n; ++i) {
-                    const uint64_t hw = hull_words(d[i].addr, d[i].len);
-                    if (wb > pre && wb < pre + hw) {
-                        const uintptr_t first = reinterpret_cast<uintptr_t>(ck->host[i]) & ~(uintptr_t)15;
-                        std::memcpy(&edge, reinterpret_cast<const uint8_t*>(first + 16 * (wb - pre) - 4), 4);
-                    }
-                    pre += hw;
+                if (e.index >= 0) {
+                    const uintptr_t first = reinterpret_cast<uintptr_t>(ck->host[e.index]) & ~(uintptr_t)15;
+                    std::memcpy(&edge, reinterpret_cast<const uint8_t*>(first + e.offset), 4);
                 }
                 __atomic_store_n(&sl.edge[p], (uint64_t)edge, __ATOMIC_RELAXED);
             }
@@ -791,9 +688,9 @@ public:
         // (tagged like a descriptor; once a checked job was seen every job
         // rewrites it, so a stale one always carries job s - 1's tag)
         if (ck || ld_acq(&checked_seen_))
-            __atomic_store_n(&sl.verdict, (ck ? ck->verdict : 0ull) | (s & 0xFFFFull) << 48, __ATOMIC_RELAXED);
+            __atomic_store_n(&sl.verdict, tag_verdict(ck ? ck->verdict : 0ull, s), __ATOMIC_RELAXED);
         const bool wt = words <= (uint64_t)kResWriteThroughWords || device_batch_running(device_);
-        __atomic_fetch_add(wt ? &wt_jobs_ : &released_jobs_, 1, __ATOMIC_RELAXED);
+        n_.add(wt ? Counters::kWtJobs : Counters::kReleasedJobs);
         // every polled slot is rewritten, so a stale half always carries job s - 1's tag
         for (uint32_t i = 0; i < n || i < (uint32_t)kPollDescs; ++i) {
             const ResDesc x = tag_desc(i < n ? d[i] : ResDesc{0, 0, 0}, s);
@@ -806,10 +703,8 @@ public:
         __atomic_store_n(&hs_[b].jobs, hs_[b].jobs + 1, __ATOMIC_RELAXED);  // (a withdrawn job is taken off again)
         __atomic_store_n(&hs_[b].checked, ck != nullptr, __ATOMIC_RELAXED);
         if (ck) __atomic_store_n(&hs_[b].checked_jobs, hs_[b].checked_jobs + 1, __ATOMIC_RELAXED);
-        __atomic_store_n(&sl.word,
-                         s | (uint64_t)n << 40 | (uint64_t)(parts - 1) << kPartShift | (wt ? kWriteThroughBit : 0) |
-                             (ck ? kCheckBit : 0) | kClaimedBit,
-                         __ATOMIC_RELEASE);
+        const uint64_t flags = (wt ? kWriteThroughBit : 0) | (ck ? kCheckBit : 0) | kClaimedBit;
+        __atomic_store_n(&sl.word, pack_job(s, n, parts, flags), __ATOMIC_RELEASE);
         *job = s;
         return KMWS_OK;
     }
@@ -819,7 +714,6 @@ public:
     // (never run: the caller launches it).
     int test(int b, uint64_t s)
     {
-        ResSlot& sl = mb_->slot[b];
         if (withdrawn_job(b, s)) return KMWS_ERR_NOT_SUPPORTED;
         if (finished(b, s)) return 1;
         const uint64_t cur = ld_acq(&inc_);
@@ -827,7 +721,6 @@ public:
             if (finished(b, s)) return 1;
             if (relaunch(cur) == 0 && withdraw(b, s, cur)) return KMWS_ERR_NOT_SUPPORTED;
         }
-        (void)sl;
         return 0;
     }
 
@@ -866,27 +759,14 @@ public:
         }
     }
 
-    uint64_t jobs() const
+    uint64_t jobs(bool checked = false) const  // jobs (checked ones) posted and not withdrawn, over the slots
     {
         uint64_t n = 0;
-        for (const SlotHost& h : hs_) n += __atomic_load_n(&h.jobs, __ATOMIC_RELAXED);
+        for (const SlotHost& h : hs_) n += __atomic_load_n(checked ? &h.checked_jobs : &h.jobs, __ATOMIC_RELAXED);
         return n;
     }
-    uint64_t checked_jobs() const
-    {
-        uint64_t n = 0;
-        for (const SlotHost& h : hs_) n += __atomic_load_n(&h.checked_jobs, __ATOMIC_RELAXED);
-        return n;
-    }
-    uint64_t variant_switches() const { return ld_acq(&variant_switches_); }
+    uint64_t count(Counters::Id i) const { return n_.get(i); }
     uint64_t launches() const { return ld_acq(&inc_); }
-    uint64_t timeouts() const { return ld_acq(&timeouts_); }
-    uint64_t withdrawn() const { return ld_acq(&withdrawn_); }
-    uint64_t unowned_posts() const { return ld_acq(&unowned_posts_); }
-    uint64_t late_posts() const { return ld_acq(&late_posts_); }
-    uint64_t drained() const { return ld_acq(&drained_); }
-    uint64_t wt_jobs() const { return ld_acq(&wt_jobs_); }
-    uint64_t released_jobs() const { return ld_acq(&released_jobs_); }
     int claimed() const { return __builtin_popcount(ld_acq(&claimed_)); }
     // Workgroup exits so far by reason (ResCtl::why), read from device memory.
     kmws_status exit_reasons(uint64_t* out, int n)
@@ -929,11 +809,17 @@ private:
     // Job s of slot b was withdrawn unrun (by its waiter, or by the release at
     // its thread's exit): its caller launches it.
     bool withdrawn_job(int b, uint64_t s) const { return ld_acq(&hs_[b].cancelled) == s; }
-    // Has the workgroup of an unfinished part of job s left grid `cur`?
+    // Part j of job s, seen from grid `cur` (all_left: its last workgroup has exited).
+    static Part part_state(const ResSlot& sl, uint32_t j, uint64_t s, uint64_t cur, bool all_left)
+    {
+        if (job_done(ld_acq(&sl.done[j]), s)) return Part::kFinished;
+        return all_left || ld_acq(&sl.gone[j]) == cur ? Part::kLeft : Part::kHeld;
+    }
+    // Has the workgroup of an unfinished part of job s left grid `cur` (which still runs)?
     static bool part_left(const ResSlot& sl, uint64_t s, uint32_t parts, uint64_t cur)
     {
         for (uint32_t j = 0; j < parts; ++j)
-            if (!job_done(ld_acq(&sl.done[j]), s) && ld_acq(&sl.gone[j]) == cur) return true;
+            if (part_state(sl, j, s, cur, false) == Part::kLeft) return true;
         return false;
     }
 
@@ -950,13 +836,11 @@ private:
         std::lock_guard<std::mutex> lk(launch_mu_);
         if (ld_acq(&inc_) != cur || hs_[b].seq != s) return false;
         const bool all_left = ld_acq(&mb_->exited) == cur;
-        for (uint32_t j = 0; j < hs_[b].parts; ++j) {
-            if (job_done(ld_acq(&sl.done[j]), s)) return false;
-            if (!all_left && ld_acq(&sl.gone[j]) != cur) return false;
-        }
+        for (uint32_t j = 0; j < hs_[b].parts; ++j)
+            if (part_state(sl, j, s, cur, all_left) != Part::kLeft) return false;
         __atomic_store_n(&sl.word, (ld_acq(&sl.word) | kCancelBit) & ~kQuitBit, __ATOMIC_RELEASE);
         __atomic_store_n(&hs_[b].cancelled, s, __ATOMIC_RELEASE);
-        __atomic_fetch_add(&withdrawn_, 1, __ATOMIC_RELAXED);
+        n_.add(Counters::kWithdrawn);
         __atomic_store_n(&hs_[b].jobs, hs_[b].jobs - 1, __ATOMIC_RELAXED);
         if (__atomic_load_n(&hs_[b].checked, __ATOMIC_RELAXED)) __atomic_store_n(&hs_[b].checked_jobs, hs_[b].checked_jobs - 1, __ATOMIC_RELAXED);
         return true;
@@ -968,7 +852,7 @@ private:
     {
         ResSlot& sl = mb_->slot[b];
         const uint32_t parts = hs_[b].parts;
-        __atomic_fetch_add(&timeouts_, 1, __ATOMIC_RELAXED);
+        n_.add(Counters::kTimeouts);
         __atomic_fetch_or(&sl.word, kQuitBit, __ATOMIC_RELEASE);
         const auto t0 = Clock::now();
         for (uint32_t spin = 0;; ++spin) {
@@ -982,8 +866,7 @@ private:
             const uint64_t cur = ld_acq(&inc_);
             const bool all_left = ld_acq(&mb_->exited) == cur;
             bool settled = true;  // every part finished, or its workgroup left
-            for (uint32_t j = 0; j < parts; ++j)
-                settled &= job_done(ld_acq(&sl.done[j]), s) || all_left || ld_acq(&sl.gone[j]) == cur;
+            for (uint32_t j = 0; j < parts; ++j) settled &= part_state(sl, j, s, cur, all_left) != Part::kHeld;
             if (settled) {
                 if (withdraw(b, s, cur)) return KMWS_ERR_NOT_SUPPORTED;  // no part ran: the caller launches
                 // some parts ran: the others run in the next grid (the quit bit cleared)
@@ -1097,12 +980,8 @@ private:
         // the instantiation is chosen per incarnation: the validating one from
         // the first checked job posted on this device on, never before
         const bool chk = ld_acq(&checked_seen_);
-        if (chk)
-            hipLaunchKernelGGL(resident_unmask_kernel<true>, dim3(nslots * kResParts), dim3(kResBlock), 0, stream_, dmb_,
-                               dctl_, cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
-        else
-            hipLaunchKernelGGL(resident_unmask_kernel<false>, dim3(nslots * kResParts), dim3(kResBlock), 0, stream_, dmb_,
-                               dctl_, cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
+        hipLaunchKernelGGL(chk ? resident_unmask_kernel<true> : resident_unmask_kernel<false>, dim3(nslots * kResParts),
+                           dim3(kResBlock), 0, stream_, dmb_, dctl_, cur + 1, nslots, exit_base_, idle_ticks_, lease_ticks_);
         if (hipGetLastError() != hipSuccess) {
             state_ = -1;
             return 0;
@@ -1142,16 +1021,10 @@ private:
         uint64_t checked_jobs = 0;  // checked jobs posted and not withdrawn
     };
     SlotHost hs_[kResSlots];
-    alignas(64) uint64_t timeouts_ = 0;
-    uint64_t withdrawn_ = 0;
-    uint64_t unowned_posts_ = 0;  // posts refused: the caller did not hold the slot
-    uint64_t wt_jobs_ = 0, released_jobs_ = 0;  // jobs posted by kind (kWriteThroughBit)
-    uint64_t late_posts_ = 0;     // jobs asked for after the thread gave its slots back (launched)
-    uint64_t drained_ = 0;        // releases that first waited for the slot's last job
+    alignas(64) Counters n_;  // off the slots' lines
     bool checked_seen_ = false;   // a checked job was posted: incarnations are the validating one from now on
     bool inc_checked_ = false;    // the latest incarnation is the validating one
     uint64_t switch_inc_ = 0;     // the last incarnation asked to leave for it
-    uint64_t variant_switches_ = 0;
 };
 
 // Every worker of the process (for the exit handler); never freed.
@@ -1199,6 +1072,15 @@ struct ThreadSlots {
 };
 thread_local ThreadSlots t_slots;
 
+// The calling thread gives its slot on `device` back, if it holds one (kept,
+// as -1, where its last job neither finished nor left in time).
+void give_back(int device)
+{
+    if (t_slots.slot1[device] <= 0) return;
+    ResidentWorker* w = __atomic_load_n(&g_by_dev[device], __ATOMIC_ACQUIRE);
+    t_slots.slot1[device] = !w || w->release(t_slots.slot1[device] - 1, t_slots.token) ? 0 : -1;
+}
+
 // Gives the thread's slots back when it exits.  Constructed at the thread's
 // first claim (or by kmws_thread_attach), so C++'s reverse order of
 // thread_local destruction runs it after every thread_local object that was
@@ -1213,10 +1095,7 @@ struct ThreadExit {
     ~ThreadExit()
     {
         t_slots.gone = true;
-        for (int d = 0; d < kMaxDevices; ++d)
-            if (t_slots.slot1[d] > 0)
-                if (ResidentWorker* w = __atomic_load_n(&g_by_dev[d], __ATOMIC_ACQUIRE))
-                    t_slots.slot1[d] = w->release(t_slots.slot1[d] - 1, t_slots.token) ? 0 : -1;
+        for (int d = 0; d < kMaxDevices; ++d) give_back(d);
     }
 };
 thread_local ThreadExit t_exit;
@@ -1267,23 +1146,22 @@ kmws_status resident_post(int device, const kmws_desc* descs, const uint8_t* dev
     };
     uint64_t bytes = 0;
     size_t k = 0;
-    for (size_t i = 0; i < n; ++i, ++k) {
-        d[k] = ResDesc{(uint64_t)(uintptr_t)(dev_base + descs[i].off), descs[i].len, descs[i].key};
-        bytes += descs[i].len;
-        if (check) {
-            ck.view[k] = view_word(check->views ? &check->views[i] : nullptr);
-            ck.host[k] = check->host_base + descs[i].off;
+    // one source: its descriptors over `dev`, the first n_views of them with a view, host addresses over `host`
+    auto add = [&](const kmws_desc* src, size_t cnt, const uint8_t* dev, const Utf8View* views, size_t n_views,
+                   const uint8_t* host) {
+        for (size_t i = 0; i < cnt; ++i, ++k) {
+            d[k] = ResDesc{(uint64_t)(uintptr_t)(dev + src[i].off), src[i].len, src[i].key};
+            bytes += src[i].len;
+            if (check) {
+                ck.view[k] = view_word(views && i < n_views ? &views[i] : nullptr);
+                ck.host[k] = host + src[i].off;
+            }
         }
-    }
-    for (size_t i = 0; i < n2; ++i, ++k) {
-        d[k] = ResDesc{(uint64_t)(uintptr_t)(dev_base2 + descs2[i].off), descs2[i].len, descs2[i].key};
-        bytes += descs2[i].len;
-        if (check) {
-            ck.view[k] = view_word(check->views2 && i < check->n_views2 ? &check->views2[i] : nullptr);
-            ck.host[k] = check->host_base2 + descs2[i].off;
-        }
-    }
-    if (bytes > max_bytes || bytes > kResMaxBytesAsync) return KMWS_ERR_NOT_SUPPORTED;
+    };
+    add(descs, n, dev_base, check ? check->views : nullptr, n, check ? check->host_base : nullptr);
+    add(descs2, n2, dev_base2, check ? check->views2 : nullptr, check ? check->n_views2 : 0,
+        check ? check->host_base2 : nullptr);
+    if (bytes > max_bytes || bytes > kResMaxBytes) return KMWS_ERR_NOT_SUPPORTED;
     if (check) ck.verdict = (uint64_t)(uintptr_t)check->verdict_dv;
     uint64_t s = 0;
     const kmws_status st = w->post(b, t_slots.token, d, (uint32_t)k, &s, check ? &ck : nullptr);
@@ -1331,10 +1209,7 @@ kmws_status kmws_resident_enable(int device, int on)
         ts.off_mask &= ~(1ull << device);
     } else {
         ts.off_mask |= 1ull << device;
-        if (ts.slot1[device] > 0) {
-            kmws::ResidentWorker* w = __atomic_load_n(&kmws::g_by_dev[device], __ATOMIC_ACQUIRE);
-            ts.slot1[device] = !w || w->release(ts.slot1[device] - 1, ts.token) ? 0 : -1;
-        }
+        kmws::give_back(device);
     }
     return KMWS_OK;
 }
@@ -1356,8 +1231,8 @@ kmws_status kmws_resident_counters(int device, int* thread_slot, int* slots_clai
     if (!w) return KMWS_ERR_INVALID_PARAM;
     if (thread_slot) *thread_slot = kmws::t_slots.slot1[device] > 0 ? kmws::t_slots.slot1[device] - 1 : -1;
     if (slots_claimed) *slots_claimed = w->claimed();
-    if (timeouts) *timeouts = w->timeouts();
-    if (withdrawn) *withdrawn = w->withdrawn();
+    if (timeouts) *timeouts = w->count(kmws::Counters::kTimeouts);
+    if (withdrawn) *withdrawn = w->count(kmws::Counters::kWithdrawn);
     return KMWS_OK;
 }
 
@@ -1366,9 +1241,9 @@ kmws_status kmws_resident_guard_counters(int device, uint64_t* unowned_posts, ui
 {
     kmws::ResidentWorker* w = kmws::worker(device);
     if (!w) return KMWS_ERR_INVALID_PARAM;
-    if (unowned_posts) *unowned_posts = w->unowned_posts();
-    if (late_posts) *late_posts = w->late_posts();
-    if (drained_releases) *drained_releases = w->drained();
+    if (unowned_posts) *unowned_posts = w->count(kmws::Counters::kUnownedPosts);
+    if (late_posts) *late_posts = w->count(kmws::Counters::kLatePosts);
+    if (drained_releases) *drained_releases = w->count(kmws::Counters::kDrained);
     return KMWS_OK;
 }
 
@@ -1376,8 +1251,8 @@ kmws_status kmws_resident_store_counters(int device, uint64_t* write_through, ui
 {
     kmws::ResidentWorker* w = kmws::worker(device);
     if (!w) return KMWS_ERR_INVALID_PARAM;
-    if (write_through) *write_through = w->wt_jobs();
-    if (released) *released = w->released_jobs();
+    if (write_through) *write_through = w->count(kmws::Counters::kWtJobs);
+    if (released) *released = w->count(kmws::Counters::kReleasedJobs);
     return KMWS_OK;
 }
 
@@ -1386,8 +1261,8 @@ kmws_status kmws_resident_utf8_counters(int device, uint64_t* checked_jobs, uint
     if (device < 0 || device >= kmws::kMaxDevices || kmws_device_count() <= device) return KMWS_ERR_INVALID_PARAM;
     kmws::ResidentWorker* w = kmws::worker(device);
     if (!w) return KMWS_ERR_INVALID_PARAM;
-    if (checked_jobs) *checked_jobs = w->checked_jobs();
-    if (variant_switches) *variant_switches = w->variant_switches();
+    if (checked_jobs) *checked_jobs = w->jobs(true);
+    if (variant_switches) *variant_switches = w->count(kmws::Counters::kVariantSwitches);
     return KMWS_OK;
 }
 
