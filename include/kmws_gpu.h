@@ -590,8 +590,9 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  *
  * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
  * checks it); the byte offset of the error.  Every payload pass has the check
- * fused in: the in-place unmask and the gather (kmws_unmask_utf8_batch and
- * kmws_gather_unmask_utf8 below), and the host path through
+ * fused in: the in-place unmask, the gather and the reframe
+ * (kmws_unmask_utf8_batch, kmws_gather_unmask_utf8 and kmws_reframe_utf8_batch
+ * below), and the host path through
  * kmws_decoder_set_utf8_check -- launched jobs and the resident grid's alike. */
 kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_desc* descs,
                                const uint16_t* flags, uint32_t n, int payload_masked,
@@ -706,7 +707,7 @@ kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, cons
  * header + payload once. */
 
 /* flags[i] of the reframe entries: emit nothing for frame i.  Honoured by
- * kmws_reframe_batch / kmws_unpack_reframe only: kmws_encode_batch and
+ * kmws_reframe_batch / kmws_unpack_reframe (and their _utf8 forms) only: kmws_encode_batch and
  * kmws_pack_headers ignore it, as they ignore every bit above KMWS_FLAG_MASK. */
 #define KMWS_FLAG_SKIP 0x8000u
 
@@ -765,6 +766,74 @@ kmws_status kmws_unpack_reframe(const uint8_t* wire, uint64_t wire_len, const ui
                                 uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys,
                                 uint8_t* dst, uint64_t dst_cap, uint64_t* wire_off,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- unmask, re-encode and UTF-8 validation in one pass over the payload ----
+ * A relay of text traffic must fail a connection that sends malformed text
+ * (1007) and must not pass its bytes on.  kmws_utf8_validate(.., payload_masked
+ * = 1, ..) on the incoming wire followed by kmws_unpack_reframe reads every
+ * payload byte twice; these entries validate the words the reframe stores from
+ * the registers that hold them.
+ *
+ * Workspace bytes: kmws_reframe_workspace_size(n, dst_cap) (rounded up to 256)
+ * plus the validator's per-frame and per-stream arrays (about 12 B per frame,
+ * 8 B per stream) -- not its tile plan. */
+size_t kmws_reframe_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams);
+
+/* The two contracts composed.  dst, wire_off and the status word are exactly
+ * what kmws_reframe_batch leaves for the same src / descs / flags / out_keys /
+ * n / dst / dst_cap (the cap rule: total > dst_cap sets status bit 1 and stores
+ * nothing; bit 4 on a look-back timeout; bytes of dst past wire_off[n] are
+ * untouched); src is never written, the descriptors need no order in src and
+ * may overlap, and a skipped frame's off / len are never used for an address.
+ * out_utf8 (n bytes) and carry_out describe the messages as they are emitted: a
+ * frame flagged KMWS_FLAG_SKIP is invisible to the check -- it gets
+ * KMWS_UTF8_NOT_TEXT and does not touch the message state, like a control
+ * frame, and its payload is never read.  Precisely, they are what
+ * kmws_utf8_validate(dst, wire_off[n], D, F, n, 1, stream_first, n_streams,
+ * carry_in, carry_out, ..) writes on the finished output wire, with, for an
+ * emitted frame, D[i] = {wire_off[i] + its header's length, descs[i].len, the
+ * outgoing key if flags[i] & KMWS_FLAG_MASK else 0} and F[i] = flags[i] & 0x1FF,
+ * and for a skipped frame D[i] = {wire_off[i], 0, 0} and F[i] = 0x89 (a FIN
+ * PING).  Text-ness comes from byte 0 of the outgoing flags.  The verdict is
+ * advisory: a BAD message is reframed like any other, and the caller drops it
+ * before dst goes to the sockets.  stream_first / carry_in / carry_out:
+ * kmws_utf8_validate's; a malformed stream_first sets status bit 1 (nothing is
+ * stored then).  With status bit 1 or 4 set out_utf8 / carry_out are not valid.
+ * Stream-ordered, no host sync, no allocation, kernel nodes only (capturable);
+ * the status word is cleared by a kernel.  KMWS_ERR_INVALID_PARAM for a NULL
+ * required pointer (wire_off and workspace always; src, descs, flags, dst,
+ * out_utf8 with frames), a misaligned src / dst, n or n_streams >= 2^31, NULL
+ * stream_first with n_streams != 1, n_streams == 0 with frames; then
+ * KMWS_ERR_BUFFER_TOO_SMALL; then KMWS_ERR_NOT_SUPPORTED without a gfx950
+ * device (no CPU fallback).  n == 0: KMWS_OK, wire_off[0] = 0, carry_out =
+ * carry_in. */
+kmws_status kmws_reframe_utf8_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
+                                    const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                                    uint64_t* wire_off,
+                                    const uint32_t* stream_first, uint32_t n_streams,
+                                    const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                    uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream);
+
+/* kmws_unpack_reframe with the validation in its payload pass.  out_desc,
+ * out_flags (required here), out_err, dst, wire_off and status bits 1, 2 and 4
+ * are exactly as after kmws_unpack_reframe; out_utf8 and carry_out are exactly
+ * kmws_reframe_utf8_batch's for the outgoing flags this call derives (the parsed
+ * header byte 0, so incoming and outgoing text-ness agree).  A frame that is
+ * not relayed -- an opcode outside relay_opcodes, or a header error -- is
+ * skipped, hence invisible to the check: KMWS_UTF8_NOT_TEXT, the message state
+ * untouched.  This differs from kmws_unpack_gather_utf8, which judges a frame
+ * with a header error as the empty frame it becomes; here as there, look at
+ * out_err (or status bit 2, with which out_utf8 / carry_out stay valid) before
+ * out_utf8.  KMWS_ERR_INVALID_PARAM for a bad mode, relay_opcodes > 0xFFFF or
+ * out_mask not 0 or 1 first; then kmws_reframe_utf8_batch's checks in its order
+ * (wire, hdr_off, out_desc, out_flags, dst, out_utf8 with frames). */
+kmws_status kmws_unpack_reframe_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                     int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                     uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys,
+                                     uint8_t* dst, uint64_t dst_cap, uint64_t* wire_off,
+                                     const uint32_t* stream_first, uint32_t n_streams,
+                                     const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- host-resident batches: pinned H2D -> kernel -> D2H pipeline ---- */
 typedef struct kmws_pipeline kmws_pipeline;

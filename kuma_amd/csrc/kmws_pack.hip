@@ -28,14 +28,16 @@
 // Relay (kmws_reframe_batch, kmws_unpack_reframe): the same copy kernels go from
 // a masked wire to the outgoing wire in one pass -- the payload XORed once with
 // incoming key ^ outgoing key, the header carrying the outgoing key, frames
-// flagged KMWS_FLAG_SKIP (control frames, header errors) emitting nothing.
+// flagged KMWS_FLAG_SKIP (control frames, header errors) emitting nothing.  Its
+// validating form (kmws_reframe_utf8_batch, kmws_unpack_reframe_utf8) checks the
+// emitted text messages in that pass, as the validating gather does.
 // Header-only pack (kmws_pack_headers, kuma's iovec form): each header into a
 // 16-byte slot, with the wire offsets after reduce_kernel.  Boundary discovery on the
 // device (kmws_find_headers_streams): the serial header-chain walk, one lane
 // per stream.
 //
-// A variant of the copy is a form ("forms" below): encode, gather, reframe and
-// the validating gather are four small structs, and every stage -- prologue,
+// A variant of the copy is a form ("forms" below): encode, gather, reframe, the
+// validating gather and the validating reframe are five small structs, and every stage -- prologue,
 // unit copy, chunk map, chunk scan, chunk copy, dense chunks -- is one kernel
 // template taking the form by value as its last argument, launched from one
 // place.  To add a variant, write its form struct (the three facts, the device
@@ -96,7 +98,7 @@ __device__ __forceinline__ void build_header(uint32_t len, uint32_t flags, uint3
 //   kHeaders: a region is the frame's header, then its payload (else: payload only);
 //   kReframe: two keys and empty regions (below);
 //   kUtf8:    the words of text messages are checked after their stores.
-// Four exist.  Everything a kernel asks of a form goes through the helpers
+// Five exist.  Everything a kernel asks of a form goes through the helpers
 // after them (flags_of, out_key, stored_key, hdr_key, copy_key, region_*).
 struct EncodeForm {  // kmws_encode_batch
     static constexpr bool kHeaders = true, kReframe = false, kUtf8 = false;
@@ -137,10 +139,28 @@ struct Utf8GatherForm {
     const uint64_t* start;
     uint32_t n;
 };
+// The validating reframe (kmws_reframe_utf8_batch, kmws_unpack_reframe_utf8):
+// the reframe's two arrays, then the validating gather's.  What differs from
+// the validating gather is what a stored word is: plain ^ the outgoing key, next
+// to header bytes, so a checked frame's bytes are recovered with its rotated
+// outgoing key (frame_out_rk, chunk_out_rk) and its bounds in output space are
+// its payload's, [start[g] + header, + len).  A skipped frame is unchecked
+// (utf8_op_byte).  The stages before the copy grid run as ReframeForm.
+// Registers: DESIGN 4 ("the validating reframe").
+struct Utf8ReframeForm {
+    static constexpr bool kHeaders = true, kReframe = true, kUtf8 = true;
+    const uint16_t* flags;
+    const uint32_t* okeys;
+    const Utf8View* views;
+    uint32_t* first_bad;
+    const kmws_desc* d;
+    const uint64_t* start;
+    uint32_t n;
+};
 template <class Form>
 constexpr bool form_exists()
 {
-    return (!Form::kReframe || Form::kHeaders) && (!Form::kUtf8 || (!Form::kHeaders && !Form::kReframe)) &&
+    return (!Form::kReframe || Form::kHeaders) && (!Form::kUtf8 || Form::kHeaders == Form::kReframe) &&
            std::is_trivially_copyable_v<Form>;
 }
 // A form without its UTF-8 part: what composes its bytes, and what the stages
@@ -148,14 +168,15 @@ constexpr bool form_exists()
 template <class Form>
 __host__ __device__ __forceinline__ auto plain_form(const Form& form)
 {
-    if constexpr (Form::kUtf8) return GatherForm{};
+    if constexpr (Form::kUtf8 && Form::kReframe) return ReframeForm{form.flags, form.okeys};
+    else if constexpr (Form::kUtf8) return GatherForm{};
     else return form;
 }
 template <class Form>
 using Plain = decltype(plain_form(std::declval<Form>()));
 static_assert(form_exists<EncodeForm>() && form_exists<GatherForm>() && form_exists<ReframeForm>() &&
-                  form_exists<Utf8GatherForm>(),
-              "encode, gather, reframe and validating gather: no other combination is written");
+                  form_exists<Utf8GatherForm>() && form_exists<Utf8ReframeForm>(),
+              "encode, gather, reframe, validating gather and validating reframe: no other combination is written");
 
 // Frame f's flags word: read only where headers are written.
 template <class Form>
@@ -675,6 +696,39 @@ __device__ __forceinline__ void check_word_frames(const u32x4& v, uint64_t a, ui
     }
 }
 
+// ---- the validating reframe (Utf8ReframeForm) ----
+// The same walk for a STORED word v of the reframe: header bytes, and each
+// frame's payload bytes masked with that frame's outgoing key.  Frame g lies at
+// [start[g] + its header, + len) in output space, and its plain bytes in the
+// word are v ^ its rotated outgoing key (byte x & 3 of it masks output byte x);
+// the bytes of v outside the frame -- headers, other frames -- come out as
+// anything and are never used (word_bad reads [off, end) only).  The dword
+// before the word again comes from the frame's own source bytes, unmasked with
+// its incoming key.  A skipped frame is unchecked (utf8_op_byte): its
+// descriptor is not followed.
+__device__ __forceinline__ void check_word_frames(const u32x4& v, uint64_t a, uint32_t g0,
+                                                  const uint8_t* __restrict__ src, const Utf8ReframeForm& u)
+{
+    for (uint32_t g = g0; g < u.n; ++g) {
+        const uint64_t s = u.start[g];
+        if (s >= a + 16u) break;
+        const Utf8View gv = u.views[g];
+        if (!(gv.w & kUtf8Checked)) continue;
+        const kmws_desc dg = u.d[g];
+        const uint32_t fl = u.flags[g];
+        const uint64_t p0 = s + region_hdr<Utf8ReframeForm>(dg.len, fl);
+        if (dg.len == 0u || p0 >= a + 16u || p0 + dg.len <= a) continue;
+        uint32_t prev = 0;
+        for (uint32_t k = 1; k <= 3u && a >= p0 + k; ++k) {
+            const uint64_t j = a - k - p0;  // payload byte j of frame g = output byte a - k
+            const uint32_t b = src[dg.off + j] ^ ((dg.key >> (8u * (uint32_t)(j & 3u))) & 0xFFu);
+            prev |= b << (8u * (4u - k));
+        }
+        const u32x4 w = v ^ rot_key(out_key(u, g, fl), p0);
+        if (plain_word_frame_bad(w, prev, a, p0, p0 + dg.len, gv.w)) report_bad(u.first_bad, gv.slot, g);
+    }
+}
+
 // A frame's unit geometry for the slot-parallel record pass (LDS), word
 // indices relative to its first unit base b0.
 struct FrameUnits {
@@ -1125,8 +1179,10 @@ __device__ __forceinline__ void prev_dwords(const u32x4 (&out)[W], int lane, uin
 // One wave per unit: kUnitW words per lane, 1 KiB per wave-instruction.
 // A unit's record and edge words hold everything of its form but the UTF-8
 // part, so the kernel is instantiated on that alone: GatherForm (every form
-// that checks nothing) and Utf8GatherForm.
-// kUtf8 (the validating gather): the unit's words are stored exactly as without
+// that checks nothing), Utf8GatherForm and Utf8ReframeForm -- the last reads,
+// besides its UTF-8 part, the unit frame's flags and outgoing key: the payload's
+// start in output space and the key its stored words still carry.
+// kUtf8 (the validating forms): the unit's words are stored exactly as without
 // it; then the words of checked frames are validated from the registers that
 // hold them, in output space.  Interior words belong to the unit's frame
 // (wave-uniform: its start, length and view are scalar loads issued ahead of
@@ -1141,7 +1197,7 @@ __global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict_
                                                       const WsHead* __restrict__ head, uint64_t unit_base,
                                                       uint32_t split, Form ug)
 {
-    static_assert(!Form::kHeaders && !Form::kReframe, "the unit copy reads the form's UTF-8 part only");
+    static_assert(Form::kUtf8 || (!Form::kHeaders && !Form::kReframe), "the unit copy reads the form's UTF-8 part only");
     const int lane = threadIdx.x & 63;
     // wave id through readfirstlane: provably uniform, so the record is one scalar load
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1179,18 +1235,36 @@ __global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict_
         unit_finish(x, lane, dst, total, R);
     } else {
         // the frame in output space and its view: scalar loads, in flight under the payload's
-        const uint64_t fs = ug.start[x.f];
+        uint64_t fs = ug.start[x.f];
         const uint32_t flen = ug.d[x.f].len;
         const Utf8View fv = ug.views[x.f];
+        // The validating reframe: the frame's payload starts behind its header, and
+        // its stored words are plain ^ ork, the outgoing key rotated for aligned
+        // output words (x.rk = the rotated incoming key ^ ork).  Scalar loads too.
+        uint32_t ork = 0;
+        if constexpr (Form::kReframe) {
+            const uint32_t ffl = ug.flags[x.f];
+            const uint32_t sk = stored_key(ug, x.f);
+            fs += region_hdr<Form>(flen, ffl);
+            ork = rot_key((ffl >> 8) & 1u ? sk : 0u, fs);
+        }
         unit_issue(x, lane, src, edge + (uint64_t)x.f * kEdgeWords, R);
         // the first owned word's first byte lies in the frame (its granule's first
         // byte does): the source holds the bytes before it wherever the frame does
+        // (the reframe: wherever its payload does -- the byte may be a header's)
         const uint64_t so = r.src + 16ull * x.klo;
-        const uint32_t lb = lookback_issue(src + so, so + (uint32_t)lane >= 4u, lane);
+        bool have = so + (uint32_t)lane >= 4u;
+        if constexpr (Form::kReframe) have = x.dst + 16ull * x.klo + (uint32_t)lane >= fs + 4u;
+        const uint32_t lb = lookback_issue(src + so, have, lane);
         // taken before the first store: a wait for its load behind them would wait for the stores too
-        const uint32_t edge_dw = lookback_dword(lb, x.rk);
+        // (unmasked with the incoming key alone)
+        const uint32_t edge_dw = lookback_dword(lb, x.rk ^ ork);
         u32x4 out[kUnitW];
         unit_finish<true>(x, lane, dst, total, R, out);
+        if constexpr (Form::kReframe) {  // the frame's payload bytes, plain, from here on
+#pragma unroll
+            for (int i = 0; i < kUnitW; ++i) out[i] = out[i] ^ ork;
+        }
         const uint32_t nslow = (x.ilo - x.klo) + (x.khi - x.ihi);
         const bool chk = (fv.w & kUtf8Checked) != 0u && flen != 0u;
         if (!chk && nslow == 0u) return;  // wave-uniform: binary, RSV1 and control frames end here
@@ -1214,7 +1288,8 @@ __global__ void __launch_bounds__(kBlock) copy_kernel(const uint8_t* __restrict_
             const uint64_t a = x.dst + 16u * k;
             const u32x4 w = i == 0 ? out[0] : (i == 1 ? out[1] : (i == 2 ? out[2] : out[3]));
             const bool edge_word = (k >= x.klo && k < x.ilo) || (k >= x.ihi && k < x.khi);
-            if (edge_word && a < total) check_word_frames(w, a, x.f, src, ug);
+            // (the reframe's walk takes the word as stored)
+            if (edge_word && a < total) check_word_frames(w ^ ork, a, x.f, src, ug);
         }
     }
 }
@@ -1309,10 +1384,29 @@ struct ChunkFrame {
     int32_t r0, p0, r1;  // region start, payload start, region end - A0
     uint32_t rk;         // rot_key(key, p0) (0: no mask); the reframe: of incoming key ^ outgoing key
     uint64_t sbase;      // source byte of output offset o = sbase + o
-    uint8_t h[16];       // the header's bytes (encode)
-    uint64_t pad;        // the validating gather: the frame's Utf8View (slot, then w)
+    uint8_t h[16];       // the header's bytes (at most 14); the validating reframe: h[15] = where the outgoing
+                         // key's bytes end in h (0: not masked) | (p0 & 3) << 4
+    uint64_t pad;        // the validating forms: the frame's Utf8View (slot, then w)
 };
 static_assert(sizeof(ChunkFrame) == 48, "ChunkFrame is three 16-byte LDS loads");
+
+// The validating reframe: a table frame's outgoing key rotated for aligned
+// output words (0: not masked) -- a stored payload byte ^ its byte is the plain
+// byte.  The key's bytes lie in the frame's header, which the table holds
+// anyway; h[15] says where.  Every other form: 0.
+template <class Form>
+__device__ __forceinline__ uint32_t chunk_out_rk(const ChunkFrame& e)
+{
+    if constexpr (!(Form::kUtf8 && Form::kReframe)) {
+        return 0u;
+    } else {
+        const uint32_t t = e.h[15], kend = t & 15u;
+        if (kend == 0u) return 0u;
+        const uint32_t key = (uint32_t)e.h[kend - 4u] | (uint32_t)e.h[kend - 3u] << 8 |
+                             (uint32_t)e.h[kend - 2u] << 16 | (uint32_t)e.h[kend - 1u] << 24;
+        return rot_key(key, t >> 4);
+    }
+}
 
 __device__ __forceinline__ int32_t rel32(uint64_t x, uint64_t A0)
 {
@@ -1418,6 +1512,8 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
             const Utf8View gv = form.views[j];
             e.pad = (uint64_t)gv.slot | (uint64_t)gv.w << 32;
             chk_lane = (gv.w & kUtf8Checked) != 0u && x.len != 0u;
+            if constexpr (Form::kReframe)  // for chunk_out_rk: a masked frame's key ends its header
+                e.h[15] = (uint8_t)((ok ? (uint32_t)(p0 - r0) : 0u) | (uint32_t)(p0 & 3u) << 4);
         }
         tab[lane] = e;
     }
@@ -1540,7 +1636,9 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
     }
     wave_lds_sync();
     // the look-back dword is taken before the first store: a wait for its load
-    // behind them would wait for the stores as well
+    // behind them would wait for the stores as well (the validating reframe: its
+    // bytes come out as the stored words do, plain ^ the frame's outgoing key,
+    // and lose that key with them below)
     uint32_t edge_dw = 0;
     if constexpr (kUtf8) edge_dw = lookback_dword(lb, tab[0].rk);
     // Pass 4: the four full-width stores, boundary words merged in.
@@ -1589,8 +1687,11 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
             if (!nd) {
                 const ChunkFrame& e = tab[(uint32_t)(jbits >> (6 * i)) & 63u];
                 const uint32_t vw = (uint32_t)(e.pad >> 32);
-                const uint32_t before = a > e.p0 ? prev[i] >> 24 : vw & 0xFFu;
-                const uint32_t hb = (outv[i].x | outv[i].y | outv[i].z | outv[i].w) & 0x80808080u;
+                // the validating reframe: outv and prev hold plain ^ ok inside this payload
+                const uint32_t ok = chunk_out_rk<Form>(e);
+                const uint32_t before = a > e.p0 ? (prev[i] ^ ok) >> 24 : vw & 0xFFu;
+                const uint32_t hb =
+                    ((outv[i].x ^ ok) | (outv[i].y ^ ok) | (outv[i].z ^ ok) | (outv[i].w ^ ok)) & 0x80808080u;
                 nd = (vw & kUtf8Checked) != 0u && (hb != 0u || before >= 0x80u);
             }
             need |= nd ? 1u << i : 0u;
@@ -1612,7 +1713,8 @@ __global__ void __launch_bounds__(kBlock) chunk_copy_kernel(const uint8_t* __res
                 if (e.r0 >= a + 16) break;
                 const uint32_t vw = (uint32_t)(e.pad >> 32);
                 if (e.r1 <= e.p0 || e.r1 <= a || !(vw & kUtf8Checked)) continue;
-                if (plain_word_frame_bad(w, pv, (uint64_t)(a + kBias), (uint64_t)(e.p0 + kBias),
+                const uint32_t ok = chunk_out_rk<Form>(e);
+                if (plain_word_frame_bad(w ^ ok, pv ^ ok, (uint64_t)(a + kBias), (uint64_t)(e.p0 + kBias),
                                          (uint64_t)(e.r1 + kBias), vw))
                     report_bad(form.first_bad, (uint32_t)e.pad, f0 + m);
             }
@@ -2135,12 +2237,25 @@ struct Utf8Launch {
     kmws_utf8_carry* carry_out;
     uint8_t* out;
 };
-static Utf8GatherForm launch_utf8_before_copy(const Utf8Launch& ul, WsHead* head, const uint8_t* src,
-                                              const kmws_desc* d, const uint64_t* start, uint32_t n, hipStream_t s)
+// The validating reframe as the host holds it: the same, and the reframe's
+// outgoing keys.  `flags` are the outgoing flags -- what the copy frames with
+// and what the check reads (in the unpack form: the workspace array that
+// reduce_kernel<HeaderReframeSize> has written by then) -- and a frame they
+// skip is a control frame to the per-frame kernels, its descriptor unread.
+// The stages before the copy grid run as ReframeForm.
+struct Utf8ReframeLaunch : Utf8Launch {
+    static constexpr bool kHeaders = true, kReframe = true, kUtf8 = true;
+    const uint32_t* okeys;
+};
+template <class Launch>
+static auto launch_utf8_before_copy(const Launch& ul, WsHead* head, const uint8_t* src, const kmws_desc* d,
+                                    const uint64_t* start, uint32_t n, hipStream_t s)
 {
-    const Utf8FrameArrays fa = launch_utf8_frame_state(ul.arrays, head, src, ul.span, d, ul.flags, n, 1,
+    const uint32_t skip = Launch::kReframe ? (uint32_t)KMWS_FLAG_SKIP : kUtf8SkipNone;
+    const Utf8FrameArrays fa = launch_utf8_frame_state(ul.arrays, head, src, ul.span, d, ul.flags, n, 1, skip,
                                                        ul.stream_first, ul.n_streams, ul.carry_in, s);
-    return Utf8GatherForm{fa.views, fa.first_bad, d, start, n};
+    if constexpr (Launch::kReframe) return Utf8ReframeForm{ul.flags, ul.okeys, fa.views, fa.first_bad, d, start, n};
+    else return Utf8GatherForm{fa.views, fa.first_bad, d, start, n};
 }
 static void launch_utf8_after_copy(const Utf8Launch& ul, uint32_t n, hipStream_t s)
 {
@@ -2355,20 +2470,21 @@ static bool have_device()
     return have;
 }
 
-// The argument checks of the seven copy entries, and the workspace carved.
+// The argument checks of the nine copy entries, and the workspace carved.
 // args_ok: the entry's own pointers and values.  Encode, gather and reframe:
 // whatever fails, BUFFER_TOO_SMALL if a workspace is there and too small for
 // the form, else INVALID_PARAM; the reframe then needs a device.  The
-// validating gather: its pointers, then utf8_stream_args_check's order.
+// validating forms: their pointers, then utf8_stream_args_check's order.
 template <class Form>
 static kmws_status copy_args_check(bool args_ok, const void* src, const void* dst, uint32_t n, uint64_t dst_cap,
                                    void* workspace, size_t workspace_bytes, CopyWs& c, const Form& form)
 {
     if constexpr (Form::kUtf8) {
         if (!args_ok) return KMWS_ERR_INVALID_PARAM;
+        const size_t need = Form::kReframe ? kmws_reframe_utf8_workspace_size(n, dst_cap, form.n_streams)
+                                           : kmws_gather_utf8_workspace_size(n, dst_cap, form.n_streams);
         const kmws_status st =
-            utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams,
-                                   kmws_gather_utf8_workspace_size(n, dst_cap, form.n_streams), workspace_bytes);
+            utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams, need, workspace_bytes);
         if (st != KMWS_OK) return st;
         return carve(workspace, workspace_bytes, n, dst_cap, c) ? KMWS_OK : KMWS_ERR_INVALID_PARAM;
     } else {
@@ -2532,6 +2648,67 @@ kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, cons
                                          n, dst_off, c, s);
     if (st != KMWS_OK) return st;
     return launch_copy_tail(wire, dst, dst_cap, dst_off, out_desc, n, c, s, form);
+}
+
+// ---- unmask, re-encode and UTF-8 check in one pass over the payload ----
+// The reframe's workspace (the copy's, then the outgoing flags), then the
+// validator's per-frame and per-stream arrays.
+size_t kmws_reframe_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
+{
+    return r256(kmws_reframe_workspace_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
+}
+static void* behind_reframe_ws(void* workspace, uint32_t n, uint64_t dst_cap)
+{
+    return workspace ? static_cast<char*>(workspace) + r256(kmws_reframe_workspace_size(n, dst_cap)) : nullptr;
+}
+
+kmws_status kmws_reframe_utf8_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
+                                    const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                                    uint64_t* wire_off, const uint32_t* stream_first, uint32_t n_streams,
+                                    const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out_utf8,
+                                    void* workspace, size_t workspace_bytes, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    CopyWs c;
+    // no source span, as for the validating gather
+    const Utf8ReframeLaunch form{{behind_reframe_ws(workspace, n, dst_cap), flags, ~0ull, stream_first, n_streams,
+                                  carry_in, carry_out, out_utf8},
+                                 out_keys};
+    const bool ptrs = wire_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
+    const kmws_status ck = copy_args_check(ptrs, src, dst, n, dst_cap, workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
+    if (n) kmws::note_device_batch(2 * dst_cap, s);
+    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
+}
+
+// kmws_unpack_reframe's launches with the per-frame kernels of the check in
+// front of the copy grid: they read the outgoing flags the reduce wrote.
+kmws_status kmws_unpack_reframe_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
+                                     int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
+                                     uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys, uint8_t* dst,
+                                     uint64_t dst_cap, uint64_t* wire_off, const uint32_t* stream_first,
+                                     uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    CopyWs c;
+    if (!mode_ok(mode) || relay_opcodes > 0xFFFFu || (out_mask != 0 && out_mask != 1)) return KMWS_ERR_INVALID_PARAM;
+    uint16_t* oflags = reinterpret_cast<uint16_t*>(behind_copy_ws(workspace, n, dst_cap));
+    const Utf8ReframeLaunch form{{behind_reframe_ws(workspace, n, dst_cap), oflags, wire_len, stream_first, n_streams,
+                                  carry_in, carry_out, out_utf8},
+                                 out_keys};
+    const bool ptrs = wire_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
+    const kmws_status ck = copy_args_check(ptrs, wire, dst, n, dst_cap, workspace, workspace_bytes, c, form);
+    if (ck != KMWS_OK) return ck;
+    if (n == 0) return launch_empty(c.head, wire_off, s, form);
+    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    kmws::note_device_batch(wire_len + dst_cap, s);
+    const HeaderReframeSize size{HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
+                                                   c.head},
+                                 oflags, relay_opcodes, (uint32_t)out_mask};
+    const kmws_status st = launch_reduce(size, n, wire_off, c, s);
+    if (st != KMWS_OK) return st;
+    return launch_copy_tail(wire, dst, dst_cap, wire_off, out_desc, n, c, s, form);
 }
 
 // head, then one 64-bit state per 2048-frame tile (pack_headers_chain_kernel)

@@ -33,7 +33,9 @@
 // pass") run kernels 1-3 and 5 as they are around a payload pass that also
 // unmasks in place.  kmws_gather_unmask_utf8 / kmws_unpack_gather_utf8
 // (kmws_pack.hip) run them around the gather's copy grid, through the host
-// launchers declared in kmws_utf8_dev.hpp.
+// launchers declared in kmws_utf8_dev.hpp; kmws_reframe_utf8_batch /
+// kmws_unpack_reframe_utf8 around the reframe's, with skip_flag naming the
+// frames that pass leaves out (control frames to kernels 1 and 3).
 #include "kmws_common.hpp"
 #include "kmws_unmask_tile.hpp"
 #include "kmws_utf8_dev.hpp"
@@ -123,6 +125,7 @@ __device__ __forceinline__ void store_carry(kmws_utf8_carry* __restrict__ c, uin
 __global__ void __launch_bounds__(kBlock) utf8_elem_kernel(const uint8_t* __restrict__ base, uint64_t span,
                                                            const kmws_desc* __restrict__ d,
                                                            const uint16_t* __restrict__ flags, uint32_t n, int masked,
+                                                           uint32_t skip_flag,
                                                            const uint32_t* __restrict__ first, uint32_t ns,
                                                            const kmws_utf8_carry* __restrict__ carry_in,
                                                            Utf8Elem* __restrict__ elems, uint32_t* __restrict__ first_bad,
@@ -139,9 +142,11 @@ __global__ void __launch_bounds__(kBlock) utf8_elem_kernel(const uint8_t* __rest
     Utf8Elem e = utf8_identity();
     if (i < n) {
         const kmws_desc df = d[i];
-        const uint32_t ob = flags[i] & 0xFFu, op = ob & 0x0Fu;
+        const uint32_t ob = utf8_op_byte(flags[i], skip_flag), op = ob & 0x0Fu;
         uint32_t nb = 0, tail = 0;
-        if (df.off > span || df.off + (uint64_t)df.len > span) {
+        if (flags[i] & skip_flag) {
+            // skipped by the pass: a control frame whose descriptor may point anywhere
+        } else if (df.off > span || df.off + (uint64_t)df.len > span) {
             atomicOr(&head->status, kStatusBadDesc);  // never read outside the span
         } else if (op < 8u) {
             nb = df.len < 3u ? df.len : 3u;
@@ -190,6 +195,7 @@ __global__ void __launch_bounds__(kBlock) utf8_scan_aggs_kernel(const Utf8Elem* 
 // The state before and after every frame.  Overwrites elems[i] with frame i's
 // view of itself (Utf8View: the payload pass and the finish read it).
 __global__ void __launch_bounds__(kBlock) utf8_ctx_kernel(const uint16_t* __restrict__ flags, uint32_t n,
+                                                          uint32_t skip_flag,
                                                           const uint32_t* __restrict__ first, uint32_t ns,
                                                           const kmws_utf8_carry* __restrict__ carry_in,
                                                           Utf8Elem* __restrict__ elems, const Utf8Elem* __restrict__ pre,
@@ -208,7 +214,7 @@ __global__ void __launch_bounds__(kBlock) utf8_ctx_kernel(const uint16_t* __rest
         bool bad = false;
         before = utf8_carry_unpack(load_carry(carry_in, s), i, &bad);
     }
-    const uint32_t ob = flags[i] & 0xFFu;
+    const uint32_t ob = utf8_op_byte(flags[i], skip_flag);
     const Utf8View v = utf8_frame_view(before, ob, i);
     elems[i] = Utf8Elem{v.slot, v.w};
     // rule (b): a checked message that ends (FIN) inside a code point.  A closing
@@ -797,16 +803,16 @@ static Utf8Arrays utf8_arrays(void* workspace, const Utf8Ws& w)
 }
 static void launch_utf8_frames(const Utf8Ws& w, const Utf8Arrays& a, const uint8_t* base, uint64_t span,
                                const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
-                               const uint32_t* stream_first, uint32_t n_streams, const kmws_utf8_carry* carry_in,
-                               hipStream_t s)
+                               uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
+                               const kmws_utf8_carry* carry_in, hipStream_t s)
 {
     const uint32_t sblk = stream_first ? (n_streams + 1u + kBlock - 1) / kBlock : 0u;
     hipLaunchKernelGGL(utf8_elem_kernel, dim3(w.nblk > sblk ? w.nblk : sblk), dim3(kBlock), 0, s, base, span, descs,
-                       flags, n, masked, stream_first, n_streams, carry_in, a.elems, a.first_bad, a.aggs, w.nblk,
-                       a.head);
+                       flags, n, masked, skip_flag, stream_first, n_streams, carry_in, a.elems, a.first_bad, a.aggs,
+                       w.nblk, a.head);
     hipLaunchKernelGGL(utf8_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, a.aggs, a.pre, w.nblk);
-    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(w.nblk), dim3(kBlock), 0, s, flags, n, stream_first, n_streams, carry_in,
-                       a.elems, a.pre, a.first_bad, a.carry_tmp);
+    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(w.nblk), dim3(kBlock), 0, s, flags, n, skip_flag, stream_first, n_streams,
+                       carry_in, a.elems, a.pre, a.first_bad, a.carry_tmp);
 }
 static void launch_utf8_finish(const Utf8Arrays& a, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                                const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out, hipStream_t s)
@@ -837,12 +843,12 @@ static Utf8Arrays frame_arrays(void* arrays, WsHead* head, const Utf8Ws& w)
 }
 Utf8FrameArrays launch_utf8_frame_state(void* arrays, WsHead* head, const uint8_t* base, uint64_t span,
                                         const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
-                                        const uint32_t* stream_first, uint32_t n_streams,
+                                        uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
                                         const kmws_utf8_carry* carry_in, hipStream_t s)
 {
     const Utf8Ws w = utf8_ws_behind(0, n, n_streams);
     const Utf8Arrays a = frame_arrays(arrays, head, w);
-    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, stream_first, n_streams, carry_in, s);
+    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, skip_flag, stream_first, n_streams, carry_in, s);
     return Utf8FrameArrays{a.views, a.first_bad};
 }
 void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
@@ -887,7 +893,7 @@ static kmws_status launch_fused(uint32_t code, uint8_t* base, uint64_t span, con
     if (ntiles)
         hipLaunchKernelGGL(utf8_edges_kernel, dim3((uint32_t)((ntiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                            base, edges, (uint32_t)ntiles);
-    launch_utf8_frames(w.u, a, base, span, descs, flags, n, 1, stream_first, n_streams, carry_in, s);
+    launch_utf8_frames(w.u, a, base, span, descs, flags, n, 1, kUtf8SkipNone, stream_first, n_streams, carry_in, s);
 
     // the apply's test for the capped launches and its means (dynamic LDS the
     // kernel does not use), with this kernel's own number of blocks per CU
@@ -936,7 +942,7 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
     uint32_t* first_bad = a.first_bad;
     const Utf8View* views = a.views;
     const int masked = payload_masked != 0;
-    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, stream_first, n_streams, carry_in, s);
+    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, kUtf8SkipNone, stream_first, n_streams, carry_in, s);
 
     const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;  // launch_plan bounded it
     Split sp;

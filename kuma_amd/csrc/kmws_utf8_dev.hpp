@@ -70,6 +70,15 @@ __device__ __forceinline__ void report_bad(uint32_t* __restrict__ first_bad, uin
 // stream order before.  The payload pass then reads views[i] (checked?, slot,
 // look-back at the frame's first byte) and reports into first_bad[slot];
 // launch_utf8_frame_finish turns both into out[] and carry_out.
+// skip_flag: the bits of flags[i] with which the payload pass leaves frame i
+// out (the reframe: KMWS_FLAG_SKIP; kUtf8SkipNone: no such bit).  Such a frame
+// is a control frame to the check -- NOT_TEXT, the message state untouched --
+// and its descriptor is neither range-checked nor followed.
+constexpr uint32_t kUtf8SkipNone = 0u;
+__device__ __forceinline__ uint32_t utf8_op_byte(uint32_t fl, uint32_t skip_flag)
+{
+    return (fl & skip_flag) ? 0x80u | KMWS_OP_PING : fl & 0xFFu;
+}
 struct Utf8FrameArrays {
     const Utf8View* views;
     uint32_t* first_bad;
@@ -77,7 +86,7 @@ struct Utf8FrameArrays {
 size_t utf8_frame_arrays_size(uint32_t n, uint32_t n_streams);
 Utf8FrameArrays launch_utf8_frame_state(void* arrays, WsHead* head, const uint8_t* base, uint64_t span,
                                         const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
-                                        const uint32_t* stream_first, uint32_t n_streams,
+                                        uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
                                         const kmws_utf8_carry* carry_in, hipStream_t s);
 void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                               const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,

@@ -52,6 +52,7 @@ EXPORTS = [
     "kmws_unmask_utf8_workspace_size", "kmws_unmask_utf8_batch", "kmws_unpack_unmask_utf8",
     "kmws_gather_utf8_workspace_size", "kmws_gather_unmask_utf8", "kmws_unpack_gather_utf8",
     "kmws_reframe_workspace_size", "kmws_reframe_batch", "kmws_unpack_reframe",
+    "kmws_reframe_utf8_workspace_size", "kmws_reframe_utf8_batch", "kmws_unpack_reframe_utf8",
 ]
 # per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
 UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
@@ -212,6 +213,10 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_reframe_workspace_size": (sz, [u32, u64]),
         "kmws_reframe_batch": (i32, [u8p, vp, vp, vp, u32, u8p, u64, vp, vp, sz, vp]),
         "kmws_unpack_reframe": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, u32, i32, vp, u8p, u64, vp, vp, sz, vp]),
+        "kmws_reframe_utf8_workspace_size": (sz, [u32, u64, u32]),
+        "kmws_reframe_utf8_batch": (i32, [u8p, vp, vp, vp, u32, u8p, u64, vp, vp, u32, vp, vp, u8p, vp, sz, vp]),
+        "kmws_unpack_reframe_utf8": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, u32, i32, vp, u8p, u64, vp, vp, u32, vp,
+                                           vp, u8p, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1177,6 +1182,75 @@ def unpack_gather_utf8(wire, hdr_off, mode: int, out_desc, out_flags, out_err, d
            "kmws_unpack_gather_utf8")
     if check and n:
         _raise_on_status(ws, stream, "kmws_unpack_gather_utf8", "dst_off")
+
+
+def reframe_utf8_workspace_size(n: int, dst_cap: int, n_streams: int = 1) -> int:
+    return lib().kmws_reframe_utf8_workspace_size(n, dst_cap, n_streams)
+
+
+def reframe_utf8(src, descs, flags, out_keys, dst, wire_off, out_utf8, ws: Workspace, stream_first=None,
+                 carry_in=None, carry_out=None, stream=None, check: bool = False) -> None:
+    """kmws_reframe_utf8_batch (stream-ordered): reframe_batch's dst / wire_off
+    and, from the same payload pass, the verdicts utf8_validate gives on the
+    emitted messages (out_utf8, uint8 (n,); a frame flagged FLAG_SKIP is
+    invisible: UTF8_NOT_TEXT) and carry_out.  stream_first / carry_in /
+    carry_out as utf8_validate's; ws: reframe_utf8_workspace_size(n,
+    dst.numel(), n_streams).  Everything is valid only when the workspace
+    status is 0 afterwards; check=True synchronizes and raises otherwise."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(src, "src", 1, dev)
+    _check_tensor(flags, "flags", 2, dev, n)
+    if out_keys is not None:
+        _check_tensor(out_keys, "out_keys", 4, dev, n)
+    _check_tensor(dst, "dst", 1, dev)
+    _check_tensor(wire_off, "wire_off", 8, dev, n + 1)
+    _check_tensor(out_utf8, "out_utf8", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
+    _check(lib().kmws_reframe_utf8_batch(src.data_ptr(), descs.data_ptr(), flags.data_ptr(), _opt(out_keys), n,
+                                         dst.data_ptr(), dst.numel(), wire_off.data_ptr(), _opt(stream_first), ns,
+                                         _opt(carry_in), _opt(carry_out), out_utf8.data_ptr(), ws.ptr, ws.nbytes,
+                                         _stream_handle(stream)), "kmws_reframe_utf8_batch")
+    if check and n:
+        _raise_on_status(ws, stream, "kmws_reframe_utf8_batch", "wire_off")
+
+
+def unpack_reframe_utf8(wire, hdr_off, mode: int, out_desc, out_flags, out_err, relay_opcodes: int, out_mask: bool,
+                        out_keys, dst, wire_off, out_utf8, ws: Workspace, wire_len: Optional[int] = None,
+                        stream_first=None, carry_in=None, carry_out=None, stream=None, check: bool = False) -> None:
+    """kmws_unpack_reframe_utf8: unpack_reframe with the UTF-8 verdicts of the
+    frames it relays (out_utf8, uint8 (n,)) from the same payload pass; ws:
+    reframe_utf8_workspace_size(n, dst.numel(), n_streams).  out_flags is
+    required; a frame that is not relayed (opcode outside relay_opcodes, header
+    error) is invisible to the check: read out_err first.  check=True
+    synchronizes and raises on a nonzero workspace status (a header error
+    included)."""
+    wire_len = wire.numel() if wire_len is None else wire_len
+    n = hdr_off.shape[0]
+    dev = wire.device
+    _check_tensor(hdr_off, "hdr_off", 8, dev, n)
+    _check_tensor(out_desc, "out_desc", 8, dev, 2 * n)
+    _check_tensor(out_flags, "out_flags", 2, dev, n)
+    if out_err is not None:
+        _check_tensor(out_err, "out_err", 1, dev, n)
+    if out_keys is not None:
+        _check_tensor(out_keys, "out_keys", 4, dev, n)
+    _check_tensor(dst, "dst", 1, dev)
+    _check_tensor(wire_off, "wire_off", 8, dev, n + 1)
+    _check_tensor(out_utf8, "out_utf8", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
+    if wire.numel() < wire_len:
+        raise ValueError("wire shorter than wire_len")
+    _check(lib().kmws_unpack_reframe_utf8(wire.data_ptr(), wire_len, hdr_off.data_ptr(), n, mode, out_desc.data_ptr(),
+                                          out_flags.data_ptr(), _opt(out_err), int(relay_opcodes),
+                                          int(bool(out_mask)), _opt(out_keys), dst.data_ptr(), dst.numel(),
+                                          wire_off.data_ptr(), _opt(stream_first), ns, _opt(carry_in),
+                                          _opt(carry_out), out_utf8.data_ptr(), ws.ptr, ws.nbytes,
+                                          _stream_handle(stream)), "kmws_unpack_reframe_utf8")
+    if check and n:
+        _raise_on_status(ws, stream, "kmws_unpack_reframe_utf8", "wire_off")
 
 
 def find_headers_into(buf, out) -> tuple:
