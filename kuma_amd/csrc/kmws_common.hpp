@@ -164,6 +164,10 @@ inline kmws_status hip_status(hipError_t e)
     return e == hipSuccess ? KMWS_OK : KMWS_ERR_FAILED;
 }
 
+// Argument tests the batch entries share.
+inline bool mode_ok(int mode) { return mode == KMWS_MODE_CLIENT || mode == KMWS_MODE_SERVER; }
+inline bool have_device() { static const bool have = kmws_device_count() > 0; return have; }
+
 // Workspace carving: sizes rounded up to 16 bytes (a vector word) and to 256.
 inline uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
 inline uint64_t r256(uint64_t x) { return (x + 255) & ~255ull; }

@@ -43,16 +43,18 @@
 // place.  To add a variant, write its form struct (the three facts, the device
 // arguments only it reads), extend form_exists and whichever of flags_of /
 // out_key / copy_key / region_* it answers differently, and add its exported
-// entry: copy_args_check, then launch_copy (or, behind a scan of its own,
-// launch_reduce and launch_copy_tail) with the form.
+// entry: its layout (kmws_workspace.hpp), a source (DescSource or WireSource,
+// the second axis) and the form, handed to copy_front.
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
 #include "kmws_utf8_dev.hpp"
+#include "kmws_workspace.hpp"
 
 namespace kmws {
 
 constexpr int kScanItems = 8;                      // frames per lane in reduce_kernel
 constexpr int kScanTile = kBlock * kScanItems;     // 2048 frames per block
+static_assert(kScanTile == kWsScanTile, "the layout's scan tile");
 
 // Header bytes of WSHandler::encodeFrameHeader as two little-endian u64
 // (byte k of the header = byte k of h[k >> 3]).
@@ -238,6 +240,7 @@ __device__ __forceinline__ uint64_t region_size(uint32_t len, uint32_t fl)
 struct V2 {
     uint64_t a, b;
 };
+static_assert(sizeof(V2) == kWsV2Bytes, "the layout's element size");
 __device__ __forceinline__ V2 operator+(V2 x, V2 y) { return V2{x.a + y.a, x.b + y.b}; }
 
 // Output words per wave unit: 4 per lane (4 KiB).  2, 3, 5, 6 and 8 words per
@@ -253,6 +256,7 @@ constexpr uint64_t kUnitAlign = 64;  // unit bases: 1 KiB aligned in the output
 constexpr uint64_t kLineBytes = 64;  // ownership granule: 64 B keeps a frame edge at 1 + 4 words
 constexpr uint64_t kLineWords = kLineBytes / 16;
 constexpr int kEdgeWords = 1 + (int)kLineWords;   // owned non-interior words per frame (at most)
+static_assert(kUnitWords == kWsUnitWords && kEdgeWords == kWsEdgeWords, "the layout's unit and edge words");
 
 // Wave units of a region of R bytes, whatever its offset: a region holds at most
 // ceil(R/kLineBytes) granule starts, and the first unit's base lies at most
@@ -546,6 +550,7 @@ struct UnitRec {
     uint32_t inner;     // interior words [ilo, ihi): ilo | ihi << 16, klo <= ilo <= ihi <= khi
 };
 static_assert(sizeof(UnitRec) == 32, "UnitRec is one s_load_dwordx8");
+static_assert(sizeof(UnitRec) == kWsUnitRecBytes, "the layout's element size");
 
 // Geometry of frame j given where its region starts (regions lie back to back:
 // frame j+1 starts where frame j's payload ends).
@@ -1320,6 +1325,7 @@ __device__ __forceinline__ u32x4 shfl16_down1(const u32x4& v)
 constexpr uint32_t kChunkW = 4;
 constexpr uint32_t kChunkWords = 64 * kChunkW;
 constexpr uint64_t kChunkBytes = 16ull * kChunkWords;
+static_assert(kChunkBytes == kWsChunkBytes, "the layout's chunk");
 constexpr uint32_t kSlowShift = 9;  // boundary-list entry: word | table frame << kSlowShift
 constexpr uint32_t kSlowWord = (1u << kSlowShift) - 1;
 static_assert(kChunkW == 4 || kChunkW == 8, "chunk: 4 or 8 words per lane");
@@ -2204,21 +2210,26 @@ __global__ void __launch_bounds__(kBlock) walk_headers_kernel(const uint8_t* __r
 // 0.722 / 0.741 units, 8 M frames of 1-300 B 0.38 / 0.48 against 0.055 /
 // 0.058, cfg3 (Zipf, 37 KiB mean, 97 % of the bytes in frames >= 16 KiB)
 // 0.733 / 0.776 against 0.775 / 0.797 (encode / gather).
-constexpr uint64_t kChunkFormBelow = 16384;
-static bool use_chunks(uint32_t n, uint64_t cap) { return n && cap / n < kChunkFormBelow; }
+// The switch is the layout's: kChunkFormBelow, copy_uses_chunks (kmws_workspace.hpp).
 // The chunk copy loads its source non-temporally for every batch (cfg4 0.77 /
 // 0.79 against 0.76 / 0.76 encode / gather with ordinary loads,
 // profiles/r04o_chunk_ab.txt) and runs without an LDS cap on its occupancy (5
 // blocks per CU, the unit form's large-frame setting, ran 0.61 against 0.75 on
 // cfg3).
+// A copy-family workspace with its layout: the launchers' pointers and counts.
 struct CopyWs {
-    WsHead* head;
-    V2* tiles;  // ntiles + 1: tile prefixes, then the totals
-    V2* grp;    // one per 256-frame row: its prefix inside the tile
-    UnitRec* rec;
-    u32x4* edge;
-    uint32_t* cmap;   // chunk -> frame holding its first byte
-    uint32_t* dense;  // chunks chunk_copy_kernel left to chunk_dense_kernel
+    void* ws;
+    CopyFamilyWs w;
+    WsHead* head() const { return at<WsHead>(ws, 0); }
+    V2* tiles() const { return at<V2>(ws, w.copy.tiles); }
+    V2* totals() const { return at<V2>(ws, w.copy.totals); }
+    V2* grp() const { return at<V2>(ws, w.copy.rows); }
+    uint64_t* states() const { return at<uint64_t>(ws, w.copy.states); }
+    UnitRec* rec() const { return at<UnitRec>(ws, w.copy.rec); }
+    u32x4* edge() const { return at<u32x4>(ws, w.copy.edge); }
+    uint32_t* cmap() const { return at<uint32_t>(ws, w.copy.cmap); }
+    uint32_t* dense() const { return at<uint32_t>(ws, w.copy.dense); }
+    uint16_t* oflags() const { return at<uint16_t>(ws, w.oflags); }
 };
 
 // The validating gather's form as the host holds it: the device part
@@ -2228,7 +2239,8 @@ struct CopyWs {
 // its finish runs after the grid.  The stages before it run as GatherForm.
 struct Utf8Launch {
     static constexpr bool kHeaders = false, kReframe = false, kUtf8 = true;
-    void* arrays;  // utf8_frame_arrays_size(n, n_streams) bytes
+    void* ws;  // the workspace and where its frame arrays lie
+    FrameArraysWs fa;
     const uint16_t* flags;
     uint64_t span;  // of the source: descriptors past it set status bit 1
     const uint32_t* stream_first;
@@ -2248,72 +2260,23 @@ struct Utf8ReframeLaunch : Utf8Launch {
     const uint32_t* okeys;
 };
 template <class Launch>
-static auto launch_utf8_before_copy(const Launch& ul, WsHead* head, const uint8_t* src, const kmws_desc* d,
-                                    const uint64_t* start, uint32_t n, hipStream_t s)
+static auto launch_utf8_before_copy(const Launch& ul, const uint8_t* src, const kmws_desc* d, const uint64_t* start,
+                                    uint32_t n, hipStream_t s)
 {
     const uint32_t skip = Launch::kReframe ? (uint32_t)KMWS_FLAG_SKIP : kUtf8SkipNone;
-    const Utf8FrameArrays fa = launch_utf8_frame_state(ul.arrays, head, src, ul.span, d, ul.flags, n, 1, skip,
+    const Utf8FrameArrays fa = launch_utf8_frame_state(ul.ws, ul.fa, src, ul.span, d, ul.flags, n, 1, skip,
                                                        ul.stream_first, ul.n_streams, ul.carry_in, s);
     if constexpr (Launch::kReframe) return Utf8ReframeForm{ul.flags, ul.okeys, fa.views, fa.first_bad, d, start, n};
     else return Utf8GatherForm{fa.views, fa.first_bad, d, start, n};
 }
-static void launch_utf8_after_copy(const Utf8Launch& ul, uint32_t n, hipStream_t s)
-{
-    launch_utf8_frame_finish(ul.arrays, n, ul.stream_first, ul.n_streams, ul.carry_in, ul.carry_out, ul.out, s);
-}
-
-static uint64_t n_tiles(uint32_t n) { return ((uint64_t)n + kScanTile - 1) / kScanTile; }
-static uint64_t n_rows(uint32_t n) { return ((uint64_t)n + kBlock - 1) / kBlock; }
-// sum of unit_bound(R_f) <= total / (16 U) + n (1 + 63 / U) (and total <= cap)
-// (rounded up to whole blocks: every wave of the copy grid reads its record)
-static uint64_t max_units(uint32_t n, uint64_t cap)
-{
-    // unit_bound(R) <= R / (16 U) + 1 + 63 / U per frame (U = kUnitWords)
-    const uint64_t u = (cap + kUnitWords * 16 - 1) / (kUnitWords * 16) + n + (63ull * n + kUnitWords - 1) / kUnitWords + 1;
-    return (u + kBlock / 64 - 1) / (kBlock / 64) * (kBlock / 64);
-}
-
-// head, tile prefixes, row prefixes (the scan's scratch)
-static size_t scan_ws_size(uint32_t n)
-{
-    return r16(sizeof(WsHead)) + (n_tiles(n) + 1) * sizeof(V2) + n_rows(n) * sizeof(V2);
-}
-static void carve_scan(char* p, uint32_t n, CopyWs& c)
-{
-    c.head = reinterpret_cast<WsHead*>(p);
-    c.tiles = reinterpret_cast<V2*>(p + r16(sizeof(WsHead)));
-    c.grp = c.tiles + n_tiles(n) + 1;
-}
-
-static size_t copy_ws_size(uint32_t n, uint64_t cap)
-{
-    if (!use_chunks(n, cap))
-        return r256(scan_ws_size(n)) + r256((uint64_t)n * kEdgeWords * 16) + max_units(n, cap) * sizeof(UnitRec);
-    return r256(scan_ws_size(n)) + r256((chunk_count(cap) + 1) * sizeof(uint32_t)) +
-           r256(chunk_count(cap) * sizeof(uint32_t));
-}
-
-static bool carve(void* ws, size_t ws_bytes, uint32_t n, uint64_t cap, CopyWs& c)
-{
-    if (!ws || ws_bytes < copy_ws_size(n, cap)) return false;
-    char* p = static_cast<char*>(ws);
-    carve_scan(p, n, c);
-    p += r256(scan_ws_size(n));  // edge words and records (or the chunk map) on whole lines
-    c.edge = reinterpret_cast<u32x4*>(p);
-    c.cmap = reinterpret_cast<uint32_t*>(p);
-    c.dense = c.cmap + r256((chunk_count(cap) + 1) * sizeof(uint32_t)) / sizeof(uint32_t);
-    p += r256((uint64_t)n * kEdgeWords * 16);
-    c.rec = reinterpret_cast<UnitRec*>(p);
-    return true;
-}
 
 // reduce_kernel (which also clears the status word), scan_tiles_kernel (n > 0).
 template <class Size>
-static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, CopyWs& c, hipStream_t s)
+static kmws_status launch_reduce(Size size, uint32_t n, uint64_t* out, const CopyWs& c, hipStream_t s)
 {
-    const uint32_t nt = (uint32_t)n_tiles(n);
-    hipLaunchKernelGGL(reduce_kernel<Size>, dim3(nt), dim3(kBlock), 0, s, size, n, c.tiles, c.grp, c.head);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(kBlock), 0, s, c.tiles, nt, out, n);
+    const uint32_t nt = c.w.copy.nt;
+    hipLaunchKernelGGL(reduce_kernel<Size>, dim3(nt), dim3(kBlock), 0, s, size, n, c.tiles(), c.grp(), c.head());
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(kBlock), 0, s, c.tiles(), nt, out, n);
     return hip_status(hipGetLastError());
 }
 
@@ -2360,38 +2323,28 @@ static kmws_status launch_empty(WsHead* head, uint64_t* start, hipStream_t s, co
 // (usually none: the grid of chunk_dense_kernel exits at once).
 template <class Form>
 static kmws_status launch_chunk_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                     const kmws_desc* d, uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s,
+                                     const kmws_desc* d, uint32_t n, const CopyWs& c, hipStream_t s,
                                      const Form& form)
 {
-    const uint64_t chunks = chunk_count(cap);  // upper bound; waves past the total exit at once
+    const uint64_t chunks = c.w.copy.n_chunks;  // upper bound; waves past the total exit at once
     const dim3 dense_grid((uint32_t)(chunks / (kBlock / 64) < 512 ? chunks / (kBlock / 64) + 1 : 512));
     auto copy = [&](auto dev) {
         using Dev = decltype(dev);
         launch_wave_slices(chunks, [&](dim3 grid, uint64_t c0) {
-            hipLaunchKernelGGL(chunk_copy_kernel<Dev>, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
-                               c.tiles + nt, c.head, c.dense, c0, kChunkSplit, dev);
+            hipLaunchKernelGGL(chunk_copy_kernel<Dev>, grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap(),
+                               c.totals(), c.head(), c.dense(), c0, kChunkSplit, dev);
         });
-        hipLaunchKernelGGL(chunk_dense_kernel<Dev>, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap,
-                           c.tiles + nt, c.head, c.dense, dev);
+        hipLaunchKernelGGL(chunk_dense_kernel<Dev>, dense_grid, dim3(kBlock), 0, s, src, dst, d, n, start, c.cmap(),
+                           c.totals(), c.head(), c.dense(), dev);
     };
     if constexpr (Form::kUtf8) {
-        copy(launch_utf8_before_copy(form, c.head, src, d, start, n, s));
-        launch_utf8_after_copy(form, n, s);
+        copy(launch_utf8_before_copy(form, src, d, start, n, s));
+        launch_utf8_frame_finish(form.ws, form.fa, n, form.stream_first, form.n_streams, form.carry_in, form.carry_out,
+                                 form.out, s);
     } else {
         copy(form);
     }
     return hip_status(hipGetLastError());
-}
-
-// The chunk form behind reduce + scan (the fused unpack-gather, whose scan
-// parses the headers): chunk_map, then the copy.
-template <class Form>
-static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                                 uint32_t n, CopyWs& c, uint32_t nt, hipStream_t s, const Form& form)
-{
-    hipLaunchKernelGGL(chunk_map_kernel<Plain<Form>>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, d, n, cap, c.head,
-                       c.tiles, nt, c.grp, start, c.cmap, plain_form(form));
-    return launch_chunk_copy(src, dst, cap, start, d, n, c, nt, s, form);
 }
 
 // The chunk form's front in one pass: one look-back pass (chunk_scan_kernel)
@@ -2402,26 +2355,29 @@ static kmws_status launch_chunks(const uint8_t* src, uint8_t* dst, uint64_t cap,
 // against 0.34-0.39 / 0.44-0.48 (encode / gather).
 template <class Form>
 static kmws_status launch_chunks_one_pass(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                          const kmws_desc* d, uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
+                                          const kmws_desc* d, uint32_t n, const CopyWs& c, hipStream_t s,
+                                          const Form& form)
 {
-    const uint32_t nt = (uint32_t)n_tiles(n);
     // head | tile totals (nt + 1) | the row-prefix area, whose first nt words hold the states
-    launch_zero_words(c.head, (r16(sizeof(WsHead)) + (uint64_t)(nt + 1) * sizeof(V2) + (uint64_t)nt * 8) / 8, s);
-    hipLaunchKernelGGL(chunk_scan_kernel<Plain<Form>>, dim3(nt), dim3(kBlock), 0, s, d, n, cap, c.head,
-                       reinterpret_cast<uint64_t*>(c.grp), c.tiles + nt, start, c.cmap, plain_form(form));
-    return launch_chunk_copy(src, dst, cap, start, d, n, c, nt, s, form);
+    launch_zero_words(c.head(), c.w.copy.zero_words, s);
+    hipLaunchKernelGGL(chunk_scan_kernel<Plain<Form>>, dim3(c.w.copy.nt), dim3(kBlock), 0, s, d, n, cap, c.head(),
+                       c.states(), c.totals(), start, c.cmap(), plain_form(form));
+    return launch_chunk_copy(src, dst, cap, start, d, n, c, s, form);
 }
 
-// The copy form after the scan: chunks (small mean) or the prologue and the
-// unit copy grid.
+// The copy form after the scan: chunk_map and the chunk copy (small mean), or
+// the prologue and the unit copy grid.
 template <class Form>
 static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start,
-                                    const kmws_desc* d, uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
+                                    const kmws_desc* d, uint32_t n, const CopyWs& c, hipStream_t s, const Form& form)
 {
-    const uint32_t nt = (uint32_t)n_tiles(n);
-    if (use_chunks(n, cap)) return launch_chunks(src, dst, cap, start, d, n, c, nt, s, form);
-    hipLaunchKernelGGL(prologue_kernel<Plain<Form>>, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, src, d, n, cap,
-                       c.head, c.tiles, nt, c.grp, start, c.rec, c.edge, plain_form(form));
+    if (c.w.copy.chunks) {
+        hipLaunchKernelGGL(chunk_map_kernel<Plain<Form>>, dim3(c.w.copy.nrows), dim3(kBlock), 0, s, d, n, cap, c.head(),
+                           c.tiles(), c.w.copy.nt, c.grp(), start, c.cmap(), plain_form(form));
+        return launch_chunk_copy(src, dst, cap, start, d, n, c, s, form);
+    }
+    hipLaunchKernelGGL(prologue_kernel<Plain<Form>>, dim3(c.w.copy.nrows), dim3(kBlock), 0, s, src, d, n, cap,
+                       c.head(), c.tiles(), c.w.copy.nt, c.grp(), start, c.rec(), c.edge(), plain_form(form));
     // Occupancy: runs of large frames stream faster with 5 blocks per CU (fewer
     // concurrent DRAM streams; capped by 32 KiB of dynamic LDS per block),
     // batches of small frames need every wave slot to hide their per-unit
@@ -2430,72 +2386,102 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
     // upper bound on the units; surplus waves exit at once.  The records and
     // edge words hold the rest of the form: copy_kernel takes its UTF-8 part only.
     auto copy = [&](auto dev) {
-        launch_wave_slices(max_units(n, cap), [&](dim3 grid, uint64_t u0) {
-            hipLaunchKernelGGL(copy_kernel<decltype(dev)>, grid, dim3(kBlock), lds_pad, s, src, dst, c.tiles + nt,
-                               c.rec, c.edge, c.head, u0, kCopySplit, dev);
+        launch_wave_slices(c.w.copy.max_units, [&](dim3 grid, uint64_t u0) {
+            hipLaunchKernelGGL(copy_kernel<decltype(dev)>, grid, dim3(kBlock), lds_pad, s, src, dst, c.totals(),
+                               c.rec(), c.edge(), c.head(), u0, kCopySplit, dev);
         });
     };
     if constexpr (Form::kUtf8) {
-        copy(launch_utf8_before_copy(form, c.head, src, d, start, n, s));
-        launch_utf8_after_copy(form, n, s);
+        copy(launch_utf8_before_copy(form, src, d, start, n, s));
+        launch_utf8_frame_finish(form.ws, form.fa, n, form.stream_first, form.n_streams, form.carry_in, form.carry_out,
+                                 form.out, s);
     } else {
         copy(GatherForm{});
     }
     return hip_status(hipGetLastError());
 }
 
-// Encode / gather: reduce (row and tile totals), scan the tile totals, the
-// prologue (offsets, edge words, unit records), the copy grid.  Four launches,
-// stream-ordered, nothing on the host in between.
+// The argument checks of the nine copy entries (args_ok: the entry's own).
+// Encode, gather and reframe: whatever fails, BUFFER_TOO_SMALL if a workspace is there and
+// too small, else INVALID_PARAM; the reframe then needs a device.  The validating forms: utf8_stream_args_check.
 template <class Form>
-static kmws_status launch_copy(const uint8_t* src, uint8_t* dst, uint64_t cap, uint64_t* start, const kmws_desc* d,
-                               uint32_t n, CopyWs& c, hipStream_t s, const Form& form)
-{
-    if (n == 0) return launch_empty(c.head, start, s, form);
-    if (use_chunks(n, cap)) return launch_chunks_one_pass(src, dst, cap, start, d, n, c, s, form);
-    const kmws_status st = launch_reduce(DescSize<Plain<Form>>{d, plain_form(form)}, n, start, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail(src, dst, cap, start, d, n, c, s, form);
-}
-
-// What lies behind the copy's workspace (NULL without one).
-static char* behind_copy_ws(void* workspace, uint32_t n, uint64_t dst_cap)
-{
-    return workspace ? static_cast<char*>(workspace) + r256(copy_ws_size(n, dst_cap)) : nullptr;
-}
-
-static bool have_device()
-{
-    static const bool have = kmws_device_count() > 0;
-    return have;
-}
-
-// The argument checks of the nine copy entries, and the workspace carved.
-// args_ok: the entry's own pointers and values.  Encode, gather and reframe:
-// whatever fails, BUFFER_TOO_SMALL if a workspace is there and too small for
-// the form, else INVALID_PARAM; the reframe then needs a device.  The
-// validating forms: their pointers, then utf8_stream_args_check's order.
-template <class Form>
-static kmws_status copy_args_check(bool args_ok, const void* src, const void* dst, uint32_t n, uint64_t dst_cap,
-                                   void* workspace, size_t workspace_bytes, CopyWs& c, const Form& form)
+static kmws_status copy_args_check(bool args_ok, const void* src, const void* dst, uint32_t n, const CopyWs& c,
+                                   size_t workspace_bytes, const Form& form)
 {
     if constexpr (Form::kUtf8) {
         if (!args_ok) return KMWS_ERR_INVALID_PARAM;
-        const size_t need = Form::kReframe ? kmws_reframe_utf8_workspace_size(n, dst_cap, form.n_streams)
-                                           : kmws_gather_utf8_workspace_size(n, dst_cap, form.n_streams);
-        const kmws_status st =
-            utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams, need, workspace_bytes);
-        if (st != KMWS_OK) return st;
-        return carve(workspace, workspace_bytes, n, dst_cap, c) ? KMWS_OK : KMWS_ERR_INVALID_PARAM;
+        return utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams, c.w.total,
+                                      workspace_bytes);
     } else {
-        const size_t need = Form::kReframe ? kmws_reframe_workspace_size(n, dst_cap) : copy_ws_size(n, dst_cap);
         if (!args_ok || (reinterpret_cast<uintptr_t>(dst) & 15u) || (reinterpret_cast<uintptr_t>(src) & 15u) ||
-            !workspace || workspace_bytes < need || !carve(workspace, workspace_bytes, n, dst_cap, c))
-            return workspace && workspace_bytes < need ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_ERR_INVALID_PARAM;
+            !c.ws || workspace_bytes < c.w.total)
+            return c.ws && workspace_bytes < c.w.total ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_ERR_INVALID_PARAM;
         return !Form::kReframe || have_device() ? KMWS_OK : KMWS_ERR_NOT_SUPPORTED;
     }
 }
-static bool mode_ok(int mode) { return mode == KMWS_MODE_CLIENT || mode == KMWS_MODE_SERVER; }
+
+// The source of a copy entry, the second axis beside the form (what is written):
+// descriptors the caller holds, or a wire whose headers the reduce parses behind a
+// status clear of its own (writing descriptors, flags, errors and, for the reframe, the
+// outgoing flags in the workspace).  traffic: the bytes noted for the batch; size: the reduce's functor.
+struct DescSource {
+    static constexpr bool kWire = false;
+    const uint8_t* src;
+    const kmws_desc* descs;
+    bool args_ok() const { return true; }
+    uint64_t traffic(uint64_t dst_cap) const { return 2 * dst_cap; }
+    template <class Form>
+    auto size(const Form& form, uint32_t, const CopyWs&) const { return DescSize<Plain<Form>>{descs, plain_form(form)}; }
+};
+struct WireSource {
+    static constexpr bool kWire = true;
+    const uint8_t* src;  // the wire
+    uint64_t wire_len;
+    const uint64_t* hdr_off;
+    int mode;
+    kmws_desc* descs;  // out, as out_flags and out_err
+    uint16_t* out_flags;
+    uint8_t* out_err;
+    uint32_t relay_opcodes = 0;  // the reframe's relay options
+    int out_mask = 0;
+    bool args_ok() const { return mode_ok(mode) && relay_opcodes <= 0xFFFFu && (out_mask == 0 || out_mask == 1); }
+    uint64_t traffic(uint64_t dst_cap) const { return wire_len + dst_cap; }
+    template <class Form>
+    auto size(const Form&, uint32_t n, const CopyWs& c) const
+    {
+        const HeaderPayloadSize hp{src, wire_len, hdr_off, n, mode, descs, out_flags, out_err, c.head()};
+        if constexpr (Form::kReframe) return HeaderReframeSize{hp, c.oflags(), relay_opcodes, (uint32_t)out_mask};
+        else return hp;
+    }
+};
+
+// Every copy entry: the checks, the empty batch, then -- stream-ordered, nothing on the
+// host in between -- the source's status clear, reduce + scan with its sizes (descriptors
+// in the chunk form: the one-pass front), the copy tail.  kmws_unpack_gather's mode test is
+// one of its pointer tests (a too-small workspace is reported first); the other wire
+// entries test their source first.  Encode and gather note an empty batch too.
+template <class Source, class Form>
+static kmws_status copy_front(const Source& in, const Form& form, bool ptrs_ok, uint8_t* dst, uint64_t dst_cap,
+                              uint64_t* start, uint32_t n, const CopyWs& c, size_t workspace_bytes, void* stream)
+{
+    constexpr bool kPlain = !Form::kReframe && !Form::kUtf8;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!kPlain && !in.args_ok()) return KMWS_ERR_INVALID_PARAM;
+    const kmws_status ck = copy_args_check(ptrs_ok && in.args_ok(), in.src, dst, n, c, workspace_bytes, form);
+    if (ck != KMWS_OK) return ck;
+    if (n == 0) {
+        if (!Source::kWire && kPlain) note_device_batch(in.traffic(dst_cap), s);
+        return launch_empty(c.head(), start, s, form);
+    }
+    if (Source::kWire && launch_zero(c.head(), sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
+    note_device_batch(in.traffic(dst_cap), s);
+    if constexpr (!Source::kWire) {
+        if (c.w.copy.chunks) return launch_chunks_one_pass(in.src, dst, dst_cap, start, in.descs, n, c, s, form);
+    }
+    const kmws_status st = launch_reduce(in.size(form, n, c), n, start, c, s);
+    if (st != KMWS_OK) return st;
+    return launch_copy_tail(in.src, dst, dst_cap, start, in.descs, n, c, s, form);
+}
 
 }  // namespace kmws
 
@@ -2503,66 +2489,45 @@ using namespace kmws;
 
 extern "C" {
 
-size_t kmws_copy_workspace_size(uint32_t n, uint64_t dst_cap) { return copy_ws_size(n, dst_cap); }
-
-// The copy's workspace, then the outgoing flags kmws_unpack_reframe derives (2 B per frame).
-size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap)
-{
-    return r256(copy_ws_size(n, dst_cap)) + r16(2ull * n);
-}
-// The copy's workspace, then the validator's per-frame and per-stream arrays.
+size_t kmws_copy_workspace_size(uint32_t n, uint64_t dst_cap) { return copy_ws(n, dst_cap).total; }
+size_t kmws_reframe_workspace_size(uint32_t n, uint64_t dst_cap) { return reframe_ws(n, dst_cap).total; }
 size_t kmws_gather_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
 {
-    return r256(copy_ws_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
+    return gather_utf8_ws(n, dst_cap, n_streams).total;
 }
+size_t kmws_reframe_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
+{
+    return reframe_utf8_ws(n, dst_cap, n_streams).total;
+}
+
 kmws_status kmws_encode_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags, uint32_t n,
                               uint8_t* dst, uint64_t dst_cap, uint64_t* wire_off, void* workspace,
                               size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    const EncodeForm form{flags};
-    const kmws_status ck = copy_args_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
-                                           workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
+    const CopyWs c{workspace, copy_family_ws(n, dst_cap, false, false, 0)};
+    return copy_front(DescSource{src, descs}, EncodeForm{flags}, wire_off && (!n || (src && descs && flags && dst)),
+                      dst, dst_cap, wire_off, n, c, workspace_bytes, stream);
 }
 
 kmws_status kmws_gather_unmask(const uint8_t* src, const kmws_desc* descs, uint32_t n, uint8_t* dst,
                                uint64_t dst_cap, uint64_t* dst_off, void* workspace, size_t workspace_bytes,
                                void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    const kmws_status ck = copy_args_check(dst_off && (!n || (src && descs && dst)), src, dst, n, dst_cap, workspace,
-                                           workspace_bytes, c, GatherForm{});
-    if (ck != KMWS_OK) return ck;
-    kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy(src, dst, dst_cap, dst_off, descs, n, c, s, GatherForm{});
+    const CopyWs c{workspace, copy_family_ws(n, dst_cap, false, false, 0)};
+    return copy_front(DescSource{src, descs}, GatherForm{}, dst_off && (!n || (src && descs && dst)), dst, dst_cap,
+                      dst_off, n, c, workspace_bytes, stream);
 }
 
-// Header parse fused into the gather: status cleared, reduce over the parsed
-// payload lengths (writing the descriptors), scan, prologue, copy -- the
-// kmws_unpack_headers launch and its status clear are gone.
+// Header parse fused into the gather: the kmws_unpack_headers launch is gone.
 kmws_status kmws_unpack_gather(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n, int mode,
                                kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err, uint8_t* dst,
                                uint64_t dst_cap, uint64_t* dst_off, void* workspace, size_t workspace_bytes,
                                void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    const kmws_status ck = copy_args_check(dst_off && (!n || (wire && hdr_off && out_desc && dst)) && mode_ok(mode),
-                                           wire, dst, n, dst_cap, workspace, workspace_bytes, c, GatherForm{});
-    if (ck != KMWS_OK) return ck;
-    if (n == 0) return launch_empty(c.head, dst_off, s, GatherForm{});
-    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    kmws::note_device_batch(wire_len + dst_cap, s);
-    const kmws_status st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags,
-                                                           out_err, c.head},
-                                         n, dst_off, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail(wire, dst, dst_cap, dst_off, out_desc, n, c, s, GatherForm{});
+    const CopyWs c{workspace, copy_family_ws(n, dst_cap, false, false, 0)};
+    const WireSource in{wire, wire_len, hdr_off, mode, out_desc, out_flags, out_err};
+    return copy_front(in, GatherForm{}, dst_off && (!n || (wire && hdr_off && out_desc && dst)), dst, dst_cap,
+                      dst_off, n, c, workspace_bytes, stream);
 }
 
 // ---- unmask and re-encode in one pass over the payload ----
@@ -2570,42 +2535,24 @@ kmws_status kmws_reframe_batch(const uint8_t* src, const kmws_desc* descs, const
                                const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
                                uint64_t* wire_off, void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    const ReframeForm form{flags, out_keys};
-    const kmws_status ck = copy_args_check(wire_off && (!n || (src && descs && flags && dst)), src, dst, n, dst_cap,
-                                           workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n) kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
+    const CopyWs c{workspace, reframe_ws(n, dst_cap)};
+    return copy_front(DescSource{src, descs}, ReframeForm{flags, out_keys},
+                      wire_off && (!n || (src && descs && flags && dst)), dst, dst_cap, wire_off, n, c,
+                      workspace_bytes, stream);
 }
 
-// The parse fused into the reframe's scan: status cleared, reduce over the
-// outgoing regions (writing the descriptors and, to the workspace, the outgoing
-// flags), scan, then the chunk map or the prologue, and the copy.
+// The parse fused into the reframe's scan: the reduce runs over the outgoing
+// regions and writes the outgoing flags to the workspace, which the copy frames with.
 kmws_status kmws_unpack_reframe(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
                                 int mode, kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err,
                                 uint32_t relay_opcodes, int out_mask, const uint32_t* out_keys, uint8_t* dst,
                                 uint64_t dst_cap, uint64_t* wire_off, void* workspace, size_t workspace_bytes,
                                 void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    if (!mode_ok(mode) || relay_opcodes > 0xFFFFu || (out_mask != 0 && out_mask != 1)) return KMWS_ERR_INVALID_PARAM;
-    uint16_t* oflags = reinterpret_cast<uint16_t*>(behind_copy_ws(workspace, n, dst_cap));
-    const ReframeForm form{oflags, out_keys};
-    const kmws_status ck = copy_args_check(wire_off && (!n || (wire && hdr_off && out_desc && dst)), wire, dst, n,
-                                           dst_cap, workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n == 0) return launch_empty(c.head, wire_off, s, form);
-    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    kmws::note_device_batch(wire_len + dst_cap, s);
-    const HeaderReframeSize size{HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
-                                                   c.head},
-                                 oflags, relay_opcodes, (uint32_t)out_mask};
-    const kmws_status st = launch_reduce(size, n, wire_off, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail(wire, dst, dst_cap, wire_off, out_desc, n, c, s, form);
+    const CopyWs c{workspace, reframe_ws(n, dst_cap)};
+    const WireSource in{wire, wire_len, hdr_off, mode, out_desc, out_flags, out_err, relay_opcodes, out_mask};
+    return copy_front(in, ReframeForm{c.oflags(), out_keys}, wire_off && (!n || (wire && hdr_off && out_desc && dst)),
+                      dst, dst_cap, wire_off, n, c, workspace_bytes, stream);
 }
 
 // ---- gather, unmask and UTF-8 check in one pass over the payload ----
@@ -2614,16 +2561,11 @@ kmws_status kmws_gather_unmask_utf8(const uint8_t* src, const kmws_desc* descs, 
                                     uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
+    const CopyWs c{workspace, gather_utf8_ws(n, dst_cap, n_streams)};
     // the plain gather has no source span: one the descriptor check never trips on
-    const Utf8Launch form{behind_copy_ws(workspace, n, dst_cap), flags, ~0ull, stream_first, n_streams, carry_in,
-                          carry_out, out_utf8};
+    const Utf8Launch form{workspace, c.w.fa, flags, ~0ull, stream_first, n_streams, carry_in, carry_out, out_utf8};
     const bool ptrs = dst_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
-    const kmws_status ck = copy_args_check(ptrs, src, dst, n, dst_cap, workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n) kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy(src, dst, dst_cap, dst_off, descs, n, c, s, form);
+    return copy_front(DescSource{src, descs}, form, ptrs, dst, dst_cap, dst_off, n, c, workspace_bytes, stream);
 }
 
 kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, const uint64_t* hdr_off, uint32_t n,
@@ -2632,53 +2574,27 @@ kmws_status kmws_unpack_gather_utf8(const uint8_t* wire, uint64_t wire_len, cons
                                     uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                     uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    if (!mode_ok(mode)) return KMWS_ERR_INVALID_PARAM;
-    const Utf8Launch form{behind_copy_ws(workspace, n, dst_cap), out_flags, wire_len, stream_first, n_streams, carry_in,
-                          carry_out, out_utf8};
+    const CopyWs c{workspace, gather_utf8_ws(n, dst_cap, n_streams)};
+    const WireSource in{wire, wire_len, hdr_off, mode, out_desc, out_flags, out_err};
+    const Utf8Launch form{workspace, c.w.fa, out_flags, wire_len, stream_first, n_streams, carry_in, carry_out,
+                          out_utf8};
     const bool ptrs = dst_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
-    const kmws_status ck = copy_args_check(ptrs, wire, dst, n, dst_cap, workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n == 0) return launch_empty(c.head, dst_off, s, form);
-    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    kmws::note_device_batch(wire_len + dst_cap, s);
-    const kmws_status st = launch_reduce(HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags,
-                                                           out_err, c.head},
-                                         n, dst_off, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail(wire, dst, dst_cap, dst_off, out_desc, n, c, s, form);
+    return copy_front(in, form, ptrs, dst, dst_cap, dst_off, n, c, workspace_bytes, stream);
 }
 
 // ---- unmask, re-encode and UTF-8 check in one pass over the payload ----
-// The reframe's workspace (the copy's, then the outgoing flags), then the
-// validator's per-frame and per-stream arrays.
-size_t kmws_reframe_utf8_workspace_size(uint32_t n, uint64_t dst_cap, uint32_t n_streams)
-{
-    return r256(kmws_reframe_workspace_size(n, dst_cap)) + utf8_frame_arrays_size(n, n_streams);
-}
-static void* behind_reframe_ws(void* workspace, uint32_t n, uint64_t dst_cap)
-{
-    return workspace ? static_cast<char*>(workspace) + r256(kmws_reframe_workspace_size(n, dst_cap)) : nullptr;
-}
-
 kmws_status kmws_reframe_utf8_batch(const uint8_t* src, const kmws_desc* descs, const uint16_t* flags,
                                     const uint32_t* out_keys, uint32_t n, uint8_t* dst, uint64_t dst_cap,
                                     uint64_t* wire_off, const uint32_t* stream_first, uint32_t n_streams,
                                     const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out_utf8,
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
+    const CopyWs c{workspace, reframe_utf8_ws(n, dst_cap, n_streams)};
     // no source span, as for the validating gather
-    const Utf8ReframeLaunch form{{behind_reframe_ws(workspace, n, dst_cap), flags, ~0ull, stream_first, n_streams,
-                                  carry_in, carry_out, out_utf8},
-                                 out_keys};
+    const Utf8ReframeLaunch form{
+        {workspace, c.w.fa, flags, ~0ull, stream_first, n_streams, carry_in, carry_out, out_utf8}, out_keys};
     const bool ptrs = wire_off && workspace && (!n || (src && descs && flags && dst && out_utf8));
-    const kmws_status ck = copy_args_check(ptrs, src, dst, n, dst_cap, workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n) kmws::note_device_batch(2 * dst_cap, s);
-    return launch_copy(src, dst, dst_cap, wire_off, descs, n, c, s, form);
+    return copy_front(DescSource{src, descs}, form, ptrs, dst, dst_cap, wire_off, n, c, workspace_bytes, stream);
 }
 
 // kmws_unpack_reframe's launches with the per-frame kernels of the check in
@@ -2690,29 +2606,15 @@ kmws_status kmws_unpack_reframe_utf8(const uint8_t* wire, uint64_t wire_len, con
                                      uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                      uint8_t* out_utf8, void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    CopyWs c;
-    if (!mode_ok(mode) || relay_opcodes > 0xFFFFu || (out_mask != 0 && out_mask != 1)) return KMWS_ERR_INVALID_PARAM;
-    uint16_t* oflags = reinterpret_cast<uint16_t*>(behind_copy_ws(workspace, n, dst_cap));
-    const Utf8ReframeLaunch form{{behind_reframe_ws(workspace, n, dst_cap), oflags, wire_len, stream_first, n_streams,
-                                  carry_in, carry_out, out_utf8},
-                                 out_keys};
+    const CopyWs c{workspace, reframe_utf8_ws(n, dst_cap, n_streams)};
+    const WireSource in{wire, wire_len, hdr_off, mode, out_desc, out_flags, out_err, relay_opcodes, out_mask};
+    const Utf8ReframeLaunch form{
+        {workspace, c.w.fa, c.oflags(), wire_len, stream_first, n_streams, carry_in, carry_out, out_utf8}, out_keys};
     const bool ptrs = wire_off && workspace && (!n || (wire && hdr_off && out_desc && out_flags && dst && out_utf8));
-    const kmws_status ck = copy_args_check(ptrs, wire, dst, n, dst_cap, workspace, workspace_bytes, c, form);
-    if (ck != KMWS_OK) return ck;
-    if (n == 0) return launch_empty(c.head, wire_off, s, form);
-    if (launch_zero(c.head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    kmws::note_device_batch(wire_len + dst_cap, s);
-    const HeaderReframeSize size{HeaderPayloadSize{wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err,
-                                                   c.head},
-                                 oflags, relay_opcodes, (uint32_t)out_mask};
-    const kmws_status st = launch_reduce(size, n, wire_off, c, s);
-    if (st != KMWS_OK) return st;
-    return launch_copy_tail(wire, dst, dst_cap, wire_off, out_desc, n, c, s, form);
+    return copy_front(in, form, ptrs, dst, dst_cap, wire_off, n, c, workspace_bytes, stream);
 }
 
-// head, then one 64-bit state per 2048-frame tile (pack_headers_chain_kernel)
-size_t kmws_pack_headers_workspace_size(uint32_t n) { return r16(sizeof(WsHead)) + n_tiles(n) * sizeof(uint64_t); }
+size_t kmws_pack_headers_workspace_size(uint32_t n) { return pack_headers_ws(n).total; }
 
 kmws_status kmws_pack_headers(const kmws_desc* descs, const uint16_t* flags, uint32_t n, uint8_t* hdr,
                               uint8_t* hl_out, uint64_t* wire_off, void* workspace, size_t workspace_bytes,
@@ -2723,19 +2625,19 @@ kmws_status kmws_pack_headers(const kmws_desc* descs, const uint16_t* flags, uin
         (wire_off && !workspace))
         return KMWS_ERR_INVALID_PARAM;
     u32x4* h = reinterpret_cast<u32x4*>(hdr);
+    const PackHeadersWs w = pack_headers_ws(n);
     if (wire_off) {
-        if (workspace_bytes < kmws_pack_headers_workspace_size(n)) return KMWS_ERR_BUFFER_TOO_SMALL;
-        WsHead* head = static_cast<WsHead*>(workspace);
-        uint64_t* st = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + r16(sizeof(WsHead)));
+        if (workspace_bytes < w.total) return KMWS_ERR_BUFFER_TOO_SMALL;
+        WsHead* head = at<WsHead>(workspace, 0);
         if (n == 0) return launch_empty(head, wire_off, s, EncodeForm{flags});
         // two launches: zero the head and the tile states, then the one-pass kernel
-        launch_zero_words(head, kmws_pack_headers_workspace_size(n) / 8, s);
-        hipLaunchKernelGGL(pack_headers_chain_kernel, dim3((uint32_t)n_tiles(n)), dim3(kBlock), 0, s, descs, flags, n, h,
-                           hl_out, wire_off, st, head);
+        launch_zero_words(head, w.total / 8, s);
+        hipLaunchKernelGGL(pack_headers_chain_kernel, dim3(w.nt), dim3(kBlock), 0, s, descs, flags, n, h, hl_out,
+                           wire_off, at<uint64_t>(workspace, w.states), head);
         return hip_status(hipGetLastError());
     }
     if (n == 0) return KMWS_OK;
-    hipLaunchKernelGGL(pack_headers_kernel, dim3((uint32_t)n_rows(n)), dim3(kBlock), 0, s, descs, flags, n, h, hl_out);
+    hipLaunchKernelGGL(pack_headers_kernel, dim3(w.nrows), dim3(kBlock), 0, s, descs, flags, n, h, hl_out);
     return hip_status(hipGetLastError());
 }
 
@@ -2758,10 +2660,9 @@ kmws_status kmws_unpack_headers(const uint8_t* wire, uint64_t wire_len, const ui
                                 void* workspace, size_t workspace_bytes, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!workspace || workspace_bytes < sizeof(WsHead) || (n && (!wire || !hdr_off || !out_desc)) ||
-        (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER))
+    if (!workspace || workspace_bytes < sizeof(WsHead) || (n && (!wire || !hdr_off || !out_desc)) || !mode_ok(mode))
         return KMWS_ERR_INVALID_PARAM;
-    WsHead* head = static_cast<WsHead*>(workspace);
+    WsHead* head = at<WsHead>(workspace, 0);
     if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
     if (n == 0) return KMWS_OK;
     hipLaunchKernelGGL(unpack_headers_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, wire, wire_len,

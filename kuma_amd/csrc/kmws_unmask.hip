@@ -16,10 +16,10 @@
 // mask (a rotated key splatted over the payload bytes of the word; header or
 // gap bytes get 0), XORs and stores whole 16-byte words.  HBM-bound: 2 bytes
 // of traffic per payload byte + 16 B per descriptor; no MFMA.
-#include "kmws_bench.h"
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
 #include "kmws_unmask_tile.hpp"
+#include "kmws_workspace.hpp"
 
 namespace kmws {
 
@@ -366,75 +366,6 @@ __global__ void __launch_bounds__(kBlock) unmask_pieces_kernel(uint8_t* __restri
     store_piece(base, x, h, v);
 }
 
-// ---- synthetic fill: byte i = byte (i & 7) of splitmix64(seed + (i >> 3)) ----
-__global__ void __launch_bounds__(kBlock) fill_synthetic_kernel(uint8_t* __restrict__ base, uint64_t bytes,
-                                                                uint64_t seed)
-{
-    const uint64_t nw = bytes >> 4;
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < nw; w += stride) {
-        const uint64_t a = splitmix64(seed + 2 * w), b = splitmix64(seed + 2 * w + 1);
-        *reinterpret_cast<u32x4*>(base + 16 * w) =
-            u32x4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (bytes & 15)) {
-        const uint64_t i = (nw << 4) + threadIdx.x;
-        base[i] = (uint8_t)(splitmix64(seed + (i >> 3)) >> (8 * (i & 7)));
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) uniform_descs_kernel(kmws_desc* __restrict__ d, uint32_t n,
-                                                               uint64_t stride, uint32_t len, uint64_t key_seed)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    kmws_desc x;
-    x.off = (uint64_t)i * stride;
-    x.len = len;
-    x.key = (uint32_t)splitmix64(key_seed + i);
-    d[i] = x;
-}
-
-// ---- independent checker: simple byte-wise restatement, not the product path ----
-constexpr int kCheckBytes = 4096;  // bytes per checker block
-
-__global__ void __launch_bounds__(kBlock) check_unmasked_kernel(const uint8_t* __restrict__ base, uint64_t bytes,
-                                                                uint64_t seed, const kmws_desc* __restrict__ d,
-                                                                uint32_t n, unsigned long long* mismatches)
-{
-    __shared__ uint32_t s_first;
-    const uint64_t nblk = (bytes + kCheckBytes - 1) / kCheckBytes;
-    unsigned long long bad = 0;
-    for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const uint64_t blk_lo = blk * kCheckBytes;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // first frame with off + len > blk_lo (binary search over sorted descs)
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (d[mid].off + d[mid].len <= blk_lo) lo = mid + 1; else hi = mid;
-        }
-        s_first = lo;
-    }
-    __syncthreads();
-    uint32_t f = s_first;
-    const uint64_t p0 = blk_lo + 16u * threadIdx.x;
-    for (int k = 0; k < 16; ++k) {
-        const uint64_t p = p0 + k;
-        if (p >= bytes) break;
-        while (f < n && d[f].off + d[f].len <= p) ++f;
-        uint8_t expect = (uint8_t)(splitmix64(seed + (p >> 3)) >> (8 * (p & 7)));
-        if (f < n && d[f].off <= p) {
-            const uint32_t key = d[f].key;
-            expect ^= (uint8_t)(key >> (8 * ((p - d[f].off) & 3)));
-        }
-        bad += base[p] != expect;
-    }
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
 // Blocks of an apply grid resident per CU, chosen together with the load depth
 // kUnmaskDepth (kmws_unmask_tile.hpp) as one pair (blocks, depth).  With every
 // load of a tile issued up front (depth 4) fewer blocks stream HBM better: 2
@@ -470,8 +401,6 @@ unsigned lds_pad_for(unsigned blocks_per_cu, unsigned static_lds)
     return per_block > static_lds ? per_block - static_lds : 0u;
 }
 
-static unsigned unmask_lds_pad_device() { return lds_pad_for(kUnmaskBlocksPerCu, kUnmaskStaticLds); }
-
 // The cap pays where tiles take the one- or two-frame paths (regions of a tile
 // or more: 16 KiB frames ran 85.5 % capped vs 79-83 % uncapped); batches of
 // smaller frames (several per tile: the LDS-staged path, whose barriers need the
@@ -482,23 +411,14 @@ bool unmask_capped(uint64_t span, uint32_t n) { return n && span / n >= ProdCfg:
 
 static unsigned unmask_lds_pad(uint64_t span, uint32_t n)
 {
-    return unmask_capped(span, n) ? unmask_lds_pad_device() : 0u;
+    return unmask_capped(span, n) ? lds_pad_for(kUnmaskBlocksPerCu, kUnmaskStaticLds) : 0u;
 }
 
-static uint32_t ilog2_u64(uint64_t x)
+// The plan's tile index is 31 bits; the workspace holds the plan.
+static kmws_status plan_fits(const PlanWs& w, size_t ws_bytes)
 {
-    uint32_t r = 0;
-    while ((1ull << r) < x) ++r;
-    return r;
-}
-
-static kmws_status check_ws(uint64_t span, size_t ws_bytes, uint64_t* ntiles_out)
-{
-    const uint64_t ntiles = (span + ProdCfg::kTile - 1) / ProdCfg::kTile;
-    if (ntiles > 0x7FFFFFFFull) return KMWS_ERR_INVALID_PARAM;
-    if (ws_bytes < sizeof(WsHead) + (ntiles + 1) * sizeof(TileRec)) return KMWS_ERR_BUFFER_TOO_SMALL;
-    *ntiles_out = ntiles;
-    return KMWS_OK;
+    if (w.ntiles > 0x7FFFFFFFull) return KMWS_ERR_INVALID_PARAM;
+    return ws_bytes < w.total ? KMWS_ERR_BUFFER_TOO_SMALL : KMWS_OK;
 }
 
 static_assert(ProdCfg::kTile == kPlanTile, "the plan's tile is the apply's");
@@ -506,14 +426,14 @@ static_assert(ProdCfg::kTile == kPlanTile, "the plan's tile is the apply's");
 kmws_status launch_plan(uint64_t span, const kmws_desc* descs, uint32_t n, void* workspace, size_t ws_bytes,
                         hipStream_t s)
 {
-    uint64_t ntiles = 0;
-    kmws_status st = check_ws(span, ws_bytes, &ntiles);
+    const PlanWs w = plan_ws(span);
+    const kmws_status st = plan_fits(w, ws_bytes);
     if (st != KMWS_OK) return st;
-    WsHead* head = static_cast<WsHead*>(workspace);
+    WsHead* head = at<WsHead>(workspace, 0);
     if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
     if (n == 0 || span == 0) return KMWS_OK;
     hipLaunchKernelGGL(tile_map_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, descs, n, span,
-                       ilog2_u64(ProdCfg::kTile), reinterpret_cast<TileRec*>(head + 1), head);
+                       ilog2_pow2((uint32_t)ProdCfg::kTile), at<TileRec>(workspace, w.map), head);
     return hip_status(hipGetLastError());
 }
 
@@ -549,36 +469,31 @@ uint32_t default_schedule(uint64_t span, uint32_t n)
     return n && span / n >= ProdCfg::kTile ? KMWS_SCHED_SPLIT4 : KMWS_SCHED_GROUPED_RUNS;
 }
 
-bool valid_schedule(uint32_t code)
+bool decode_schedule(uint32_t code, Schedule* out)
 {
-    Split sp;
     const uint32_t store = code & (kSchedTemporal | kSchedNT);
-    return split_of(code & kKindMask, &sp) && store != (kSchedTemporal | kSchedNT) &&
+    out->temporal = (code & kSchedTemporal) != 0;
+    return split_of(code & kKindMask, &out->split) && store != (kSchedTemporal | kSchedNT) &&
            (code & ~(kKindMask | kSchedTemporal | kSchedNT)) == 0;
 }
 
-bool temporal_stores(uint32_t code) { return (code & kSchedTemporal) != 0; }
-
-static kmws_status launch_apply(uint32_t code, uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
-                                const void* workspace, size_t ws_bytes, hipStream_t s)
+kmws_status launch_apply(const Schedule& sc, uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
+                         const void* workspace, size_t ws_bytes, hipStream_t s)
 {
-    Split sp;
-    if (!valid_schedule(code) || !split_of(code & kKindMask, &sp)) return KMWS_ERR_INVALID_PARAM;
-    uint64_t ntiles = 0;
-    kmws_status st = check_ws(span, ws_bytes, &ntiles);
+    const PlanWs w = plan_ws(span);
+    const kmws_status st = plan_fits(w, ws_bytes);
     if (st != KMWS_OK) return st;
     if (n == 0 || span == 0) return KMWS_OK;
-    const WsHead* head = static_cast<const WsHead*>(workspace);
-    const TileRec* map = reinterpret_cast<const TileRec*>(head + 1);
+    const WsHead* head = at<const WsHead>(workspace, 0);
+    const TileRec* map = at<const TileRec>(workspace, w.map);
     const uint64_t nfull = span / ProdCfg::kTile;
-    const bool temporal = temporal_stores(code);
     const unsigned lds_pad = unmask_lds_pad(span, n);
-    const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
-    launch_split_grid(nfull, lds_pad, temporal, [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
+    const TileMapping tm = tile_mapping((uint32_t)nfull, sc.split);
+    launch_split_grid(nfull, lds_pad, sc.temporal, [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
         hipLaunchKernelGGL((unmask_split_kernel<kUnmaskV, decltype(two)::value, decltype(nt)::value>), grid,
                            dim3(kBlock), pad, s, base, descs, n, map, head, tm, b0);
     });
-    if (ntiles > nfull)  // the partial last tile
+    if (w.ntiles > nfull)  // the partial last tile
         hipLaunchKernelGGL(unmask_tail_kernel<kUnmaskV>, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, map, head,
                            (uint32_t)nfull);
     return hip_status(hipGetLastError());
@@ -614,12 +529,12 @@ kmws_status launch_unpack_plan(const uint8_t* wire, uint64_t wire_len, const uin
                                kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err, void* workspace,
                                hipStream_t s)
 {
-    WsHead* head = static_cast<WsHead*>(workspace);
+    WsHead* head = at<WsHead>(workspace, 0);
     if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
     if (n == 0) return KMWS_OK;
     hipLaunchKernelGGL(unpack_plan_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, wire, wire_len, hdr_off,
-                       n, mode, out_desc, out_flags, out_err, ilog2_u64(ProdCfg::kTile),
-                       reinterpret_cast<TileRec*>(head + 1), head);
+                       n, mode, out_desc, out_flags, out_err, ilog2_pow2((uint32_t)ProdCfg::kTile),
+                       at<TileRec>(workspace, plan_ws(wire_len).map), head);
     return hip_status(hipGetLastError());
 }
 }  // namespace kmws
@@ -630,8 +545,7 @@ extern "C" {
 
 size_t kmws_unmask_workspace_size(uint64_t span)
 {
-    const uint64_t ntiles = (span + ProdCfg::kTile - 1) / ProdCfg::kTile;
-    return sizeof(WsHead) + (size_t)(ntiles + 1) * sizeof(TileRec);  // + the map's sentinel
+    return plan_ws(span).total;
 }
 
 kmws_status kmws_unmask_batch(uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
@@ -662,7 +576,9 @@ kmws_status kmws_unmask_apply_sched(uint8_t* base, uint64_t span, const kmws_des
     if (bad_args(base, descs, n, workspace)) return KMWS_ERR_INVALID_PARAM;
     const uint32_t code = schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule;
     kmws::note_device_batch(2 * span, static_cast<hipStream_t>(stream));
-    return launch_apply(code, base, span, descs, n, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    Schedule sc;
+    if (!decode_schedule(code, &sc)) return KMWS_ERR_INVALID_PARAM;
+    return launch_apply(sc, base, span, descs, n, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int kmws_unmask_default_schedule(uint64_t span, uint32_t n) { return (int)default_schedule(span, n); }
@@ -671,25 +587,17 @@ kmws_status kmws_unpack_unmask(uint8_t* wire, uint64_t wire_len, const uint64_t*
                                kmws_desc* out_desc, uint16_t* out_flags, uint8_t* out_err, void* workspace,
                                size_t workspace_bytes, int schedule, void* stream)
 {
-    if (bad_args(wire, out_desc, n, workspace) || (n && !hdr_off) ||
-        (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER))
+    if (bad_args(wire, out_desc, n, workspace) || (n && !hdr_off) || !mode_ok(mode)) return KMWS_ERR_INVALID_PARAM;
+    Schedule sc;
+    if (!decode_schedule(schedule < 0 ? default_schedule(wire_len, n) : (uint32_t)schedule, &sc))
         return KMWS_ERR_INVALID_PARAM;
-    const uint32_t code = schedule < 0 ? default_schedule(wire_len, n) : (uint32_t)schedule;
-    if (!valid_schedule(code)) return KMWS_ERR_INVALID_PARAM;
-    uint64_t ntiles = 0;
-    kmws_status st = check_ws(wire_len, workspace_bytes, &ntiles);
+    kmws_status st = plan_fits(plan_ws(wire_len), workspace_bytes);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    WsHead* head = static_cast<WsHead*>(workspace);
-    if (launch_zero(head, sizeof(WsHead), s) != KMWS_OK) return KMWS_ERR_FAILED;
-    if (n == 0) return KMWS_OK;
+    st = launch_unpack_plan(wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err, workspace, s);
+    if (st != KMWS_OK || n == 0) return st;
     kmws::note_device_batch(2 * wire_len, s);
-    hipLaunchKernelGGL(unpack_plan_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, wire, wire_len, hdr_off,
-                       n, mode, out_desc, out_flags, out_err, ilog2_u64(ProdCfg::kTile),
-                       reinterpret_cast<TileRec*>(head + 1), head);
-    st = hip_status(hipGetLastError());
-    if (st != KMWS_OK) return st;
-    return launch_apply(code, wire, wire_len, out_desc, n, workspace, workspace_bytes, s);
+    return launch_apply(sc, wire, wire_len, out_desc, n, workspace, workspace_bytes, s);
 }
 
 // Times each schedule on the caller's batch, two launches per timing (XOR
@@ -722,10 +630,11 @@ int kmws_unmask_autotune(uint8_t* base, uint64_t span, const kmws_desc* descs, u
     for (int rep = 0; rep < 3 && st == KMWS_OK; ++rep) {
         for (int ki = 0; ki < kKinds; ++ki) {
             for (int si = 0; si < 2; ++si) {
-                const uint32_t g = kinds[ki] | stores[si];
+                Schedule sc;
+                (void)decode_schedule(kinds[ki] | stores[si], &sc);
                 if (hipEventRecord(e0, s) != hipSuccess) { st = KMWS_ERR_FAILED; break; }
                 for (int k = 0; k < 2 && st == KMWS_OK; ++k)
-                    st = launch_apply(g, base, span, descs, n, workspace, workspace_bytes, s);
+                    st = launch_apply(sc, base, span, descs, n, workspace, workspace_bytes, s);
                 if (st != KMWS_OK || hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) {
                     st = st != KMWS_OK ? st : KMWS_ERR_FAILED;
                     break;
@@ -784,138 +693,6 @@ int kmws_device_count(void)
         if (hipGetDeviceProperties(&p, i) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++good;
     }
     return good;
-}
-
-// ---------------- bench / test support (include/kmws_bench.h) ----------------
-
-void* kmws_arena_alloc(uint64_t bytes, int device, int* contiguous)
-{
-    if (contiguous) *contiguous = 0;
-    if (bytes == 0) return nullptr;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) return nullptr;
-    if (device != prev && hipSetDevice(device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous) == hipSuccess && p) {
-        if (contiguous) *contiguous = 1;
-    } else {
-        (void)hipGetLastError();
-        p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-        }
-    }
-    if (device != prev) (void)hipSetDevice(prev);
-    return p;
-}
-
-void kmws_arena_free(void* p, int device)
-{
-    if (!p) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    if (device != prev) (void)hipSetDevice(device);
-    (void)hipFree(p);
-    if (device != prev) (void)hipSetDevice(prev);
-}
-
-int64_t kmws_arena_place(uint8_t* arena, uint64_t arena_bytes, uint64_t span, uint64_t step, void* stream,
-                         float* frac_out, uint32_t max_out)
-{
-    // Offsets 0, step, 2 step, ... with offset + span <= arena_bytes.  The probe
-    // batch: uniform 64 KiB frames over the span (contents are whatever the arena
-    // holds; XOR applied twice leaves them unchanged); an offset scores the better
-    // of the split-4 and split-8 schedules (which one leads depends on the
-    // placement, and kmws_unmask_autotune then picks among all).
-    constexpr uint64_t kFrame = 65536;
-    if (!arena || span == 0 || span > arena_bytes || step == 0 || (step & 15u) ||
-        (reinterpret_cast<uintptr_t>(arena) & 15u) || span / kFrame > 0xFFFFFFFFull)
-        return KMWS_ERR_INVALID_PARAM;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = (uint32_t)((span + kFrame - 1) / kFrame);
-    const size_t ws_bytes = kmws_unmask_workspace_size(span);
-    kmws_desc* d = nullptr;
-    void* ws = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int64_t result = KMWS_ERR_FAILED;
-    if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * sizeof(kmws_desc)) != hipSuccess ||
-        hipMalloc(&ws, ws_bytes) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess) {
-        (void)hipGetLastError();
-    } else {
-        hipLaunchKernelGGL(uniform_descs_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d, n, kFrame,
-                           (uint32_t)kFrame, 0x706c6163ull);
-        // the last frame ends at the span (uniform_descs gives every frame kFrame bytes)
-        const uint32_t last_len = (uint32_t)(span - (uint64_t)(n - 1) * kFrame);
-        kmws_status st = hip_status(hipMemcpyAsync(&d[n - 1].len, &last_len, sizeof(last_len),
-                                                   hipMemcpyHostToDevice, s));
-        if (st == KMWS_OK) st = hip_status(hipStreamSynchronize(s));
-        float best = 1e30f;
-        uint64_t pick = 0;
-        uint32_t k = 0;
-        for (uint64_t off = 0; st == KMWS_OK && off + span <= arena_bytes; off += step, ++k) {
-            float t = 1e30f;
-            for (int rep = 0; rep < 4 && st == KMWS_OK; ++rep) {  // min of two pairs per schedule
-                st = launch_plan(span, d, n, ws, ws_bytes, s);
-                if (st == KMWS_OK) st = hip_status(hipEventRecord(e0, s));
-                const uint32_t g = (rep & 1 ? KMWS_SCHED_SPLIT8 : KMWS_SCHED_SPLIT4) | kSchedNT;
-                for (int i = 0; i < 2 && st == KMWS_OK; ++i)
-                    st = launch_apply(g, arena + off, span, d, n, ws, ws_bytes, s);
-                if (st == KMWS_OK) st = hip_status(hipEventRecord(e1, s));
-                if (st == KMWS_OK) st = hip_status(hipEventSynchronize(e1));
-                float ms = 0;
-                if (st == KMWS_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < t) t = ms;
-            }
-            if (st != KMWS_OK) break;
-            // fraction of the 8 TB/s HBM peak: 2 passes x (2 span + 16 n) bytes
-            if (frac_out && k < max_out) frac_out[k] = (float)(2.0 * (2.0 * span + 16.0 * n) / (t * 1e-3) / 8e12);
-            if (t < best) {
-                best = t;
-                pick = off;
-            }
-        }
-        uint32_t status = 0;
-        if (st == KMWS_OK) st = hip_status(hipMemcpy(&status, ws, sizeof(status), hipMemcpyDeviceToHost));
-        result = st != KMWS_OK ? (int64_t)st : (status != 0 ? (int64_t)KMWS_ERR_FAILED : (int64_t)pick);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (ws) (void)hipFree(ws);
-    if (d) (void)hipFree(d);
-    return result;
-}
-
-kmws_status kmws_fill_synthetic(uint8_t* base, uint64_t bytes, uint64_t seed, void* stream)
-{
-    if (!base && bytes) return KMWS_ERR_INVALID_PARAM;
-    if ((reinterpret_cast<uintptr_t>(base) & 15u)) return KMWS_ERR_INVALID_PARAM;
-    if (bytes == 0) return KMWS_OK;
-    hipLaunchKernelGGL(fill_synthetic_kernel, dim3(8192), dim3(kBlock), 0, static_cast<hipStream_t>(stream), base,
-                       bytes, seed);
-    return hip_status(hipGetLastError());
-}
-
-kmws_status kmws_fill_uniform_descs(kmws_desc* descs, uint32_t n, uint64_t stride, uint32_t len,
-                                    uint64_t key_seed, void* stream)
-{
-    if (!descs && n) return KMWS_ERR_INVALID_PARAM;
-    if (n == 0) return KMWS_OK;
-    hipLaunchKernelGGL(uniform_descs_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0,
-                       static_cast<hipStream_t>(stream), descs, n, stride, len, key_seed);
-    return hip_status(hipGetLastError());
-}
-
-kmws_status kmws_check_unmasked(const uint8_t* base, uint64_t bytes, uint64_t seed, const kmws_desc* descs,
-                                uint32_t n, unsigned long long* mismatches, void* stream)
-{
-    if ((!base && bytes) || !mismatches) return KMWS_ERR_INVALID_PARAM;
-    if (bytes == 0) return KMWS_OK;
-    uint64_t nb = (bytes + kCheckBytes - 1) / kCheckBytes;
-    if (nb > 65536) nb = 65536;  // grid-stride beyond this
-    hipLaunchKernelGGL(check_unmasked_kernel, dim3((uint32_t)nb), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                       base, bytes, seed, descs, n, mismatches);
-    return hip_status(hipGetLastError());
 }
 
 }  // extern "C"

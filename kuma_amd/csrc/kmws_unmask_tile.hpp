@@ -280,11 +280,17 @@ using ProdCfg = UnmaskCfg<kUnmaskV>;
 constexpr uint32_t kUnmaskStaticLds = ProdCfg::kCap * (8 + 8 + 4);  // s_off, s_end, s_key
 
 // ---- host side (kmws_unmask.hip) ----
-// A schedule code of kmws_unmask_apply_sched is valid; it asks for temporal
-// stores; the default of a batch nobody tuned.
-bool valid_schedule(uint32_t code);
-bool temporal_stores(uint32_t code);
+// A schedule code of kmws_unmask_apply_sched, decoded once per call (false: not
+// a valid code); default_schedule: the code of a batch nobody tuned.
+struct Schedule {
+    Split split;
+    bool temporal;
+};
+bool decode_schedule(uint32_t code, Schedule* out);
 uint32_t default_schedule(uint64_t span, uint32_t n);
+// The apply's launches behind a launched plan (kmws_arena_place times them).
+kmws_status launch_apply(const Schedule& sc, uint8_t* base, uint64_t span, const kmws_desc* descs, uint32_t n,
+                         const void* workspace, size_t ws_bytes, hipStream_t s);
 // The batch takes the capped launches (mean region of a tile or more: the one-
 // and two-frame mask paths); the dynamic LDS a capped launch asks for so that
 // exactly blocks_per_cu blocks with static_lds bytes of static LDS share a CU.

@@ -40,35 +40,15 @@
 #include "kmws_unmask_tile.hpp"
 #include "kmws_utf8_dev.hpp"
 #include "kmws_utf8_rule.hpp"
+#include "kmws_workspace.hpp"
 
 namespace kmws {
 
 constexpr uint32_t kStatusBadStreams = kStatusBadDesc;  // a malformed stream_first: the same caller error bit
 
-// ---- workspace: the unmask plan's, then the per-frame and per-stream arrays ----
-struct Utf8Ws {
-    size_t plan_bytes;  // WsHead + tile records
-    size_t first_bad, elems, aggs, pre, carry, total;
-    uint32_t nblk;  // scan blocks of kBlock frames
-};
-// plan_bytes: what lies in front of the arrays (0: nothing, utf8_frame_arrays_size)
-static Utf8Ws utf8_ws_behind(size_t plan_bytes, uint32_t n, uint32_t n_streams)
-{
-    Utf8Ws w;
-    w.nblk = (n + kBlock - 1) / kBlock;
-    w.plan_bytes = plan_bytes;
-    w.first_bad = r16(w.plan_bytes);
-    w.elems = w.first_bad + r16((size_t)n * 4);
-    w.aggs = w.elems + r16((size_t)n * 8);
-    w.pre = w.aggs + r16((size_t)w.nblk * 8);
-    w.carry = w.pre + r16((size_t)w.nblk * 8);
-    w.total = w.carry + r16((size_t)n_streams * 8);
-    return w;
-}
-static Utf8Ws utf8_ws(uint64_t span, uint32_t n, uint32_t n_streams)
-{
-    return utf8_ws_behind(kmws_unmask_workspace_size(span), n, n_streams);
-}
+// The workspaces (utf8_ws, fused_ws) are laid out in kmws_workspace.hpp.
+static_assert(sizeof(Utf8Elem) == kWsUtf8ElemBytes && sizeof(Utf8View) == sizeof(Utf8Elem),
+              "the layout's element size; the views replace the elements in place");
 
 // Inclusive scan of one element per lane over the block (Hillis-Steele in LDS);
 // s[] holds the inclusive values on return.
@@ -461,20 +441,6 @@ static_assert(kUtf8V == kUnmaskV && kFusedRows == 4 * kUtf8V, "the validator's t
 constexpr unsigned kFusedBlocksPerCu = 4;
 constexpr unsigned kFusedStaticLds = kUnmaskStaticLds + 4u * (unsigned)kFusedRows;  // + s_row
 
-struct FusedWs {
-    Utf8Ws u;
-    size_t edges, total;
-};
-static FusedWs fused_ws(uint64_t span, uint32_t n, uint32_t n_streams)
-{
-    FusedWs w;
-    w.u = utf8_ws(span, n, n_streams);
-    const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;
-    w.edges = r16(w.u.total);
-    w.total = w.edges + r16((size_t)ntiles * 4);
-    return w;
-}
-
 // edges[t]: the dword before tile t as it lies in memory before the payload
 // pass (tile 0 has none: 0).
 __global__ void __launch_bounds__(kBlock) utf8_edges_kernel(const uint8_t* __restrict__ base,
@@ -760,12 +726,6 @@ kmws_status launch_unmask_pieces_utf8(uint8_t* base, const kmws_desc* descs, con
     return hip_status(hipGetLastError());
 }
 
-static bool have_device()
-{
-    static const bool have = kmws_device_count() > 0;
-    return have;
-}
-
 kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
                                    uint32_t n_streams, size_t need, size_t have)
 {
@@ -779,39 +739,30 @@ kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, u
 }
 
 // The per-frame kernels of a batch (1-3 of the list above) and the finish (5),
-// on a workspace laid out by utf8_ws behind a plan that has been launched.
+// on the frame arrays of a workspace whose status word has been cleared.
 struct Utf8Arrays {
-    WsHead* head;
-    const TileRec* map;
     uint32_t* first_bad;
     Utf8Elem *elems, *aggs, *pre, *carry_tmp;
     const Utf8View* views;
+    uint32_t nblk;
 };
-static Utf8Arrays utf8_arrays(void* workspace, const Utf8Ws& w)
+static Utf8Arrays utf8_arrays(void* workspace, const FrameArraysWs& w)
 {
-    uint8_t* wsb = static_cast<uint8_t*>(workspace);
-    Utf8Arrays a;
-    a.head = static_cast<WsHead*>(workspace);
-    a.map = reinterpret_cast<const TileRec*>(a.head + 1);
-    a.first_bad = reinterpret_cast<uint32_t*>(wsb + w.first_bad);
-    a.elems = reinterpret_cast<Utf8Elem*>(wsb + w.elems);
-    a.aggs = reinterpret_cast<Utf8Elem*>(wsb + w.aggs);
-    a.pre = reinterpret_cast<Utf8Elem*>(wsb + w.pre);
-    a.carry_tmp = reinterpret_cast<Utf8Elem*>(wsb + w.carry);
-    a.views = reinterpret_cast<const Utf8View*>(a.elems);
-    return a;
+    return Utf8Arrays{at<uint32_t>(workspace, w.first_bad), at<Utf8Elem>(workspace, w.elems),
+                      at<Utf8Elem>(workspace, w.aggs),      at<Utf8Elem>(workspace, w.pre),
+                      at<Utf8Elem>(workspace, w.carry),     at<const Utf8View>(workspace, w.elems), w.nblk};
 }
-static void launch_utf8_frames(const Utf8Ws& w, const Utf8Arrays& a, const uint8_t* base, uint64_t span,
+static void launch_utf8_frames(const Utf8Arrays& a, WsHead* head, const uint8_t* base, uint64_t span,
                                const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
                                uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
                                const kmws_utf8_carry* carry_in, hipStream_t s)
 {
     const uint32_t sblk = stream_first ? (n_streams + 1u + kBlock - 1) / kBlock : 0u;
-    hipLaunchKernelGGL(utf8_elem_kernel, dim3(w.nblk > sblk ? w.nblk : sblk), dim3(kBlock), 0, s, base, span, descs,
+    hipLaunchKernelGGL(utf8_elem_kernel, dim3(a.nblk > sblk ? a.nblk : sblk), dim3(kBlock), 0, s, base, span, descs,
                        flags, n, masked, skip_flag, stream_first, n_streams, carry_in, a.elems, a.first_bad, a.aggs,
-                       w.nblk, a.head);
-    hipLaunchKernelGGL(utf8_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, a.aggs, a.pre, w.nblk);
-    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(w.nblk), dim3(kBlock), 0, s, flags, n, skip_flag, stream_first, n_streams,
+                       a.nblk, head);
+    hipLaunchKernelGGL(utf8_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, a.aggs, a.pre, a.nblk);
+    hipLaunchKernelGGL(utf8_ctx_kernel, dim3(a.nblk), dim3(kBlock), 0, s, flags, n, skip_flag, stream_first, n_streams,
                        carry_in, a.elems, a.pre, a.first_bad, a.carry_tmp);
 }
 static void launch_utf8_finish(const Utf8Arrays& a, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
@@ -821,8 +772,8 @@ static void launch_utf8_finish(const Utf8Arrays& a, uint32_t n, const uint32_t* 
     hipLaunchKernelGGL(utf8_finish_kernel, dim3((fin_lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n,
                        stream_first, n_streams, a.views, a.first_bad, a.carry_tmp, carry_in, carry_out, out);
 }
-static kmws_status launch_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
-                                     hipStream_t s)
+kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                                   hipStream_t s)
 {
     if (carry_out && n_streams)
         hipLaunchKernelGGL(utf8_carry_copy_kernel, dim3((n_streams + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
@@ -831,37 +782,21 @@ static kmws_status launch_carry_copy(uint32_t n_streams, const kmws_utf8_carry* 
 }
 
 // ---- for the validating gather (kmws_pack.hip, declared in kmws_utf8_dev.hpp) ----
-size_t utf8_frame_arrays_size(uint32_t n, uint32_t n_streams) { return utf8_ws_behind(0, n, n_streams).total; }
-
-// The arrays stand alone (no plan in front of them); the status word is the caller's.
-static Utf8Arrays frame_arrays(void* arrays, WsHead* head, const Utf8Ws& w)
-{
-    Utf8Arrays a = utf8_arrays(arrays, w);
-    a.head = head;
-    a.map = nullptr;
-    return a;
-}
-Utf8FrameArrays launch_utf8_frame_state(void* arrays, WsHead* head, const uint8_t* base, uint64_t span,
+Utf8FrameArrays launch_utf8_frame_state(void* workspace, const FrameArraysWs& fa, const uint8_t* base, uint64_t span,
                                         const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
                                         uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
                                         const kmws_utf8_carry* carry_in, hipStream_t s)
 {
-    const Utf8Ws w = utf8_ws_behind(0, n, n_streams);
-    const Utf8Arrays a = frame_arrays(arrays, head, w);
-    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, skip_flag, stream_first, n_streams, carry_in, s);
+    const Utf8Arrays a = utf8_arrays(workspace, fa);
+    launch_utf8_frames(a, at<WsHead>(workspace, 0), base, span, descs, flags, n, masked, skip_flag, stream_first,
+                       n_streams, carry_in, s);
     return Utf8FrameArrays{a.views, a.first_bad};
 }
-void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                              const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
-                              hipStream_t s)
+void launch_utf8_frame_finish(void* workspace, const FrameArraysWs& fa, uint32_t n, const uint32_t* stream_first,
+                              uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                              uint8_t* out, hipStream_t s)
 {
-    const Utf8Arrays a = frame_arrays(arrays, nullptr, utf8_ws_behind(0, n, n_streams));
-    launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
-}
-kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
-                                   hipStream_t s)
-{
-    return launch_carry_copy(n_streams, carry_in, carry_out, s);
+    launch_utf8_finish(utf8_arrays(workspace, fa), n, stream_first, n_streams, carry_in, carry_out, out, s);
 }
 
 // The argument checks of the fused entries: the schedule to run (`code`), then
@@ -869,42 +804,42 @@ kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* ca
 // KMWS_ERR_INVALID_PARAM, so the schedule's test stands in front.
 static kmws_status fused_check(const uint8_t* base, bool ptrs_ok, uint32_t n, const uint32_t* stream_first,
                                uint32_t n_streams, uint64_t span, int schedule, size_t workspace_bytes,
-                               const FusedWs& w, uint32_t* code)
+                               const FusedWs& w, Schedule* sc)
 {
-    *code = schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule;
-    if (!valid_schedule(*code)) return KMWS_ERR_INVALID_PARAM;
+    if (!decode_schedule(schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule, sc))
+        return KMWS_ERR_INVALID_PARAM;
     return utf8_stream_args_check(ptrs_ok, base, nullptr, n, stream_first, n_streams, n ? w.total : 0, workspace_bytes);
 }
 
 // Behind a launched plan (and the header parse, if any): the look-back
 // pre-pass, the per-frame kernels on the still-masked payload, the fused
 // payload pass on the apply's grids, the finish.
-static kmws_status launch_fused(uint32_t code, uint8_t* base, uint64_t span, const kmws_desc* descs,
+static kmws_status launch_fused(const Schedule& sc, uint8_t* base, uint64_t span, const kmws_desc* descs,
                                 const uint16_t* flags, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                                 const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
                                 void* workspace, const FusedWs& w, hipStream_t s)
 {
-    Split sp;
-    if (!split_of(code & 0xFFu, &sp)) return KMWS_ERR_INVALID_PARAM;
-    const Utf8Arrays a = utf8_arrays(workspace, w.u);
-    uint32_t* edges = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(workspace) + w.edges);
-    const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;  // launch_plan bounded it
+    const Utf8Arrays a = utf8_arrays(workspace, w.u.fa);
+    WsHead* head = at<WsHead>(workspace, 0);
+    const TileRec* map = at<const TileRec>(workspace, w.u.plan.map);
+    uint32_t* edges = at<uint32_t>(workspace, w.edges);
+    const uint64_t ntiles = w.u.plan.ntiles;  // launch_plan bounded it
     const uint64_t nfull = span / kPlanTile;
     if (ntiles)
         hipLaunchKernelGGL(utf8_edges_kernel, dim3((uint32_t)((ntiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                            base, edges, (uint32_t)ntiles);
-    launch_utf8_frames(w.u, a, base, span, descs, flags, n, 1, kUtf8SkipNone, stream_first, n_streams, carry_in, s);
+    launch_utf8_frames(a, head, base, span, descs, flags, n, 1, kUtf8SkipNone, stream_first, n_streams, carry_in, s);
 
     // the apply's test for the capped launches and its means (dynamic LDS the
     // kernel does not use), with this kernel's own number of blocks per CU
     const unsigned lds_pad = unmask_capped(span, n) ? lds_pad_for(kFusedBlocksPerCu, kFusedStaticLds) : 0u;
-    const TileMapping tm = tile_mapping((uint32_t)nfull, sp);
-    launch_split_grid(nfull, lds_pad, temporal_stores(code), [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
+    const TileMapping tm = tile_mapping((uint32_t)nfull, sc.split);
+    launch_split_grid(nfull, lds_pad, sc.temporal, [&](auto two, auto nt, dim3 grid, uint32_t b0, unsigned pad) {
         hipLaunchKernelGGL((unmask_utf8_split_kernel<decltype(two)::value, decltype(nt)::value>), grid, dim3(kBlock), pad,
-                           s, base, descs, n, a.map, a.head, a.views, a.first_bad, edges, tm, b0);
+                           s, base, descs, n, map, head, a.views, a.first_bad, edges, tm, b0);
     });
     if (ntiles > nfull)  // the partial last tile
-        hipLaunchKernelGGL(unmask_utf8_tail_kernel, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, a.map, a.head,
+        hipLaunchKernelGGL(unmask_utf8_tail_kernel, dim3(1), dim3(kBlock), 0, s, base, span, descs, n, map, head,
                            a.views, a.first_bad, edges, (uint32_t)nfull);
     launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
     return hip_status(hipGetLastError());
@@ -931,30 +866,28 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
                                             n_streams, n ? w.total : 0, workspace_bytes);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);  // every stream's state passes through
-    st = launch_plan(span, descs, n, workspace, w.plan_bytes, s);
+    if (n == 0) return launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);  // every stream's state passes through
+    st = launch_plan(span, descs, n, workspace, w.plan.total, s);
     if (st != KMWS_OK) return st;
     note_device_batch(span, s);
 
-    const Utf8Arrays a = utf8_arrays(workspace, w);
-    WsHead* head = a.head;
-    const TileRec* map = a.map;
-    uint32_t* first_bad = a.first_bad;
-    const Utf8View* views = a.views;
+    const Utf8Arrays a = utf8_arrays(workspace, w.fa);
+    WsHead* head = at<WsHead>(workspace, 0);
+    const TileRec* map = at<const TileRec>(workspace, w.plan.map);
     const int masked = payload_masked != 0;
-    launch_utf8_frames(w, a, base, span, descs, flags, n, masked, kUtf8SkipNone, stream_first, n_streams, carry_in, s);
+    launch_utf8_frames(a, head, base, span, descs, flags, n, masked, kUtf8SkipNone, stream_first, n_streams, carry_in,
+                       s);
 
-    const uint64_t ntiles = (span + kPlanTile - 1) / kPlanTile;  // launch_plan bounded it
     Split sp;
     (void)split_of(KMWS_SCHED_SPLIT4, &sp);
     const TileMapping tm = tile_mapping((uint32_t)(span / kPlanTile), sp);  // the partial last tile maps to itself
-    launch_split_grid(ntiles, 0u, false, [&](auto, auto, dim3 grid, uint32_t b0, unsigned) {
+    launch_split_grid(w.plan.ntiles, 0u, false, [&](auto, auto, dim3 grid, uint32_t b0, unsigned) {  // launch_plan bounded it
         if (masked)
             hipLaunchKernelGGL(utf8_payload_kernel<true>, grid, dim3(kBlock), 0, s, base, span, descs, n, map, head,
-                               views, first_bad, tm, b0);
+                               a.views, a.first_bad, tm, b0);
         else
             hipLaunchKernelGGL(utf8_payload_kernel<false>, grid, dim3(kBlock), 0, s, base, span, descs, n, map, head,
-                               views, first_bad, tm, b0);
+                               a.views, a.first_bad, tm, b0);
     });
     launch_utf8_finish(a, n, stream_first, n_streams, carry_in, carry_out, out, s);
     return hip_status(hipGetLastError());
@@ -971,16 +904,16 @@ kmws_status kmws_unmask_utf8_batch(uint8_t* base, uint64_t span, const kmws_desc
                                    void* workspace, size_t workspace_bytes, int schedule, void* stream)
 {
     const FusedWs w = fused_ws(span, n, n_streams);
-    uint32_t code = 0;
+    Schedule sc;
     kmws_status st = fused_check(base, base && descs && flags && out && workspace, n, stream_first, n_streams, span,
-                                 schedule, workspace_bytes, w, &code);
+                                 schedule, workspace_bytes, w, &sc);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);
-    st = launch_plan(span, descs, n, workspace, w.u.plan_bytes, s);
+    if (n == 0) return launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
+    st = launch_plan(span, descs, n, workspace, w.u.plan.total, s);
     if (st != KMWS_OK) return st;
     note_device_batch(2 * span, s);
-    return launch_fused(code, base, span, descs, flags, n, stream_first, n_streams, carry_in, carry_out, out, workspace,
+    return launch_fused(sc, base, span, descs, flags, n, stream_first, n_streams, carry_in, carry_out, out, workspace,
                         w, s);
 }
 
@@ -991,18 +924,18 @@ kmws_status kmws_unpack_unmask_utf8(uint8_t* wire, uint64_t wire_len, const uint
                                     size_t workspace_bytes, int schedule, void* stream)
 {
     const FusedWs w = fused_ws(wire_len, n, n_streams);
-    uint32_t code = 0;
-    if (mode != KMWS_MODE_CLIENT && mode != KMWS_MODE_SERVER) return KMWS_ERR_INVALID_PARAM;
-    const bool fits = (wire_len + kPlanTile - 1) / kPlanTile <= 0x7FFFFFFFull;  // the plan's tile index
+    Schedule sc;
+    if (!mode_ok(mode)) return KMWS_ERR_INVALID_PARAM;
+    const bool fits = w.u.plan.ntiles <= 0x7FFFFFFFull;  // the plan's tile index
     kmws_status st = fused_check(wire, wire && hdr_off && out_desc && out_flags && out_utf8 && workspace && fits, n,
-                                 stream_first, n_streams, wire_len, schedule, workspace_bytes, w, &code);
+                                 stream_first, n_streams, wire_len, schedule, workspace_bytes, w, &sc);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) return launch_carry_copy(n_streams, carry_in, carry_out, s);
+    if (n == 0) return launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);
     st = launch_unpack_plan(wire, wire_len, hdr_off, n, mode, out_desc, out_flags, out_err, workspace, s);
     if (st != KMWS_OK) return st;
     note_device_batch(2 * wire_len, s);
-    return launch_fused(code, wire, wire_len, out_desc, out_flags, n, stream_first, n_streams, carry_in, carry_out,
+    return launch_fused(sc, wire, wire_len, out_desc, out_flags, n, stream_first, n_streams, carry_in, carry_out,
                         out_utf8, workspace, w, s);
 }
 

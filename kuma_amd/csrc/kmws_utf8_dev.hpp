@@ -7,6 +7,7 @@
 #pragma once
 #include "kmws_common.hpp"
 #include "kmws_utf8_rule.hpp"
+#include "kmws_workspace.hpp"
 
 namespace kmws {
 
@@ -62,11 +63,11 @@ __device__ __forceinline__ void report_bad(uint32_t* __restrict__ first_bad, uin
 }
 
 // ---- the per-frame kernels around a payload pass of another file ----
-// `arrays`: utf8_frame_arrays_size(n, n_streams) bytes, 16-byte aligned.
-// launch_utf8_frame_state runs utf8_elem_kernel, utf8_scan_aggs_kernel and
+// `fa`: where the frame arrays lie in `workspace` (kmws_workspace.hpp), whose
+// WsHead holds the status word.  launch_utf8_frame_state runs utf8_elem_kernel, utf8_scan_aggs_kernel and
 // utf8_ctx_kernel on the payloads at base + descs[i].off (masked != 0: still
 // masked with descs[i].key); a descriptor outside [0, span) or a malformed
-// stream_first ORs status bit 1 into *head, which the caller has cleared in
+// stream_first ORs status bit 1 into the head, which the caller has cleared in
 // stream order before.  The payload pass then reads views[i] (checked?, slot,
 // look-back at the frame's first byte) and reports into first_bad[slot];
 // launch_utf8_frame_finish turns both into out[] and carry_out.
@@ -83,14 +84,13 @@ struct Utf8FrameArrays {
     const Utf8View* views;
     uint32_t* first_bad;
 };
-size_t utf8_frame_arrays_size(uint32_t n, uint32_t n_streams);
-Utf8FrameArrays launch_utf8_frame_state(void* arrays, WsHead* head, const uint8_t* base, uint64_t span,
+Utf8FrameArrays launch_utf8_frame_state(void* workspace, const FrameArraysWs& fa, const uint8_t* base, uint64_t span,
                                         const kmws_desc* descs, const uint16_t* flags, uint32_t n, int masked,
                                         uint32_t skip_flag, const uint32_t* stream_first, uint32_t n_streams,
                                         const kmws_utf8_carry* carry_in, hipStream_t s);
-void launch_utf8_frame_finish(void* arrays, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                              const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out, uint8_t* out,
-                              hipStream_t s);
+void launch_utf8_frame_finish(void* workspace, const FrameArraysWs& fa, uint32_t n, const uint32_t* stream_first,
+                              uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
+                              uint8_t* out, hipStream_t s);
 // carry_out = carry_in for every stream (an empty batch).
 kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                    hipStream_t s);

@@ -47,7 +47,7 @@ def header_len(length, mask):
 
 
 def use_chunks(n, cap):
-    """The host's form rule (use_chunks in kmws_pack.hip)."""
+    """The host's form rule (copy_uses_chunks in kmws_workspace.hpp)."""
     return n > 0 and cap // n < kChunkFormBelow
 
 

@@ -142,7 +142,7 @@ def wire_and_offsets(rng, kind, n, mode_mask=1):
 def test_unpack_gather_roundtrip(T, kind, room):
     """room = spare arena capacity per frame: 20000 puts the mean region bound
     past 16 KiB, so the gather takes the unit form; 0 the chunk form for every
-    kind with a smaller mean (kmws_pack.hip, use_chunks)."""
+    kind with a smaller mean (kmws_workspace.hpp, copy_uses_chunks)."""
     from kuma_amd import kmws
     rng = np.random.default_rng(zlib.crc32(str(kind).encode()))
     wire, wire_off, src, offs, lens, flags, keys = wire_and_offsets(rng, kind, 250 if kind != "max" else 6)

@@ -19,7 +19,7 @@ CSRC = os.path.join(ROOT, "kuma_amd", "csrc")
 
 def _constexpr_defs():
     text = ""
-    for name in ("kmws_common.hpp", "kmws_pack.hip"):
+    for name in ("kmws_common.hpp", "kmws_workspace.hpp", "kmws_pack.hip"):
         with open(os.path.join(CSRC, name)) as f:
             text += f.read()
     text = re.sub(r"//[^\n]*", "", text)
@@ -41,8 +41,9 @@ def test_constants_match_the_kernel_source():
     got = {name: _value(name, defs) for name in pec.CONSTANTS}
     assert got == pec.CONSTANTS
     # the form rule the device tests select the form with
-    with open(os.path.join(CSRC, "kmws_pack.hip")) as f:
-        assert re.search(r"use_chunks\(uint32_t n, uint64_t cap\)\s*\{\s*return n && cap / n < kChunkFormBelow;", f.read())
+    with open(os.path.join(CSRC, "kmws_workspace.hpp")) as f:
+        assert re.search(r"copy_uses_chunks\(uint32_t n, uint64_t cap\)\s*\{\s*return n && cap / n < kChunkFormBelow;",
+                         f.read())
 
 
 def _variants():
