@@ -231,13 +231,40 @@ void kmws_decoder_set_in_place(kmws_decoder* dec, int on);
  * the GPU step of a call or generation fails, its frames are dropped as
  * without the check, and the message that was open across them is no longer
  * checkable: its later frames report KMWS_UTF8_NOT_TEXT until the next message
- * head.  Not done: the reason text of a CLOSE frame (at most 123 bytes: the
- * host checks it) and the byte offset of the error. */
+ * head.  Not done: the reason text of a CLOSE frame (kmws_decoder_set_proto_check
+ * below judges it: KMWS_PROTO_CLOSE_REASON) and the byte offset of the error. */
 void kmws_decoder_set_utf8_check(kmws_decoder* dec, int on);
 /* The KMWS_UTF8_* value of a frame, valid during its frame callback.  Also
  * exported as a function for callers that cannot use a macro. */
 uint8_t kmws_frame_utf8(const kmws_frame_hdr* hdr);
 #define kmws_frame_utf8(h) ((h)->reserved)
+
+/* Opt-in check of the frame sequence and the CLOSE body on the host path (RFC
+ * 6455 5.2, 5.4, 5.5, 7.4), off by default; NULL is a no-op.  With it on,
+ * kmws_decoder_feed and kmws_decoder_feed_deferred / kmws_rx_batch_flush /
+ * kmws_rx_batch_poll (so RxLoop too) judge every frame by the rules of
+ * kmws_proto_check (below, with the KMWS_PROTO_* values) for one stream, the
+ * stream being everything this decoder was fed since it was created or
+ * kmws_decoder_reset, which returns the state to IDLE.  rsv_allowed: the RSV
+ * bits (0x40, 0x20, 0x10) a data message's head may carry; other bits of it
+ * are ignored.  kmws_decoder_frame_proto reads the verdict of the frame whose
+ * callback is running on dec; outside a callback, with the check off, or for
+ * NULL it is 0 (== KMWS_PROTO_OK).  The verdict is advisory: bytes, callbacks
+ * and return values do not change; the application closes with 1002, or with
+ * 1007 for KMWS_PROTO_CLOSE_REASON.
+ *
+ * How: the parser computes the verdict when it completes a frame -- the state
+ * is one byte and a CLOSE payload is at most 125 contiguous bytes by then,
+ * unmasked into a private copy for the check -- so this check needs no GPU.
+ * The verdict waits with the queued frame, beside its UTF-8 view, and is
+ * published on the decoder just before the frame's callback and cleared after
+ * it.  A frame that is parsed but never delivered (its GPU step failed, or
+ * kmws_rx_batch_discard) still counts for the state.  On this path
+ * KMWS_PROTO_HEADER, KMWS_PROTO_CONTROL and KMWS_PROTO_AFTER_CLOSE cannot
+ * occur: the decoder stops at a header error, at a control frame without FIN
+ * or above 125 bytes, and after a CLOSE, as kuma does. */
+void kmws_decoder_set_proto_check(kmws_decoder* dec, int on, uint32_t rsv_allowed);
+int  kmws_decoder_frame_proto(const kmws_decoder* dec);
 
 /* WSHandler::handleDataMask(key, KMBuffer&) (WSHandler.cpp:312-322) and, with
  * nseg == 1, handleDataMask(key, data, len) (:303-310) for HOST buffers: the
@@ -588,8 +615,8 @@ size_t kmws_utf8_workspace_size(uint64_t span, uint32_t n, uint32_t n_streams);
  * well-formed string, or (b) it has FIN and they end inside a code point --
  * which an empty FIN frame can do.
  *
- * Not done here: the reason text of a CLOSE frame (at most 123 bytes: the host
- * checks it); the byte offset of the error.  Every payload pass has the check
+ * Not done here: the reason text of a CLOSE frame (kmws_proto_check below
+ * judges it: KMWS_PROTO_CLOSE_REASON); the byte offset of the error.  Every payload pass has the check
  * fused in: the in-place unmask, the gather and the reframe
  * (kmws_unmask_utf8_batch, kmws_gather_unmask_utf8 and kmws_reframe_utf8_batch
  * below), and the host path through
@@ -599,6 +626,80 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
                                const uint32_t* stream_first, uint32_t n_streams,
                                const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- frame-sequence and CLOSE rules per stream (opt-in; RFC 6455 5.2, 5.4, 5.5, 7.4) ----
+ * kuma's WSHandler accepts sequences the RFC forbids -- a CONTINUE with no open
+ * message (the TODO at WSHandler.cpp:131), a new data head inside a message,
+ * reserved opcodes, RSV bits nobody negotiated, any CLOSE body -- and so does
+ * this codec, byte for byte.  A server that wants to answer 1002 (and 1007 for a
+ * CLOSE reason) without walking every stream's frames on the CPU calls this on
+ * the descriptors of a device batch.  Nothing else changes behaviour.
+ *
+ * Per-frame result.  A stream is IDLE, OPEN (a data message is unfinished),
+ * CLOSED or FAILED; every value but OK, and AFTER_*, moves it to FAILED: */
+#define KMWS_PROTO_OK             0
+#define KMWS_PROTO_RSV            1  /* an RSV bit outside rsv_allowed on a data head (opcode 1, 2), or any
+                                        on a CONTINUE or control frame */
+#define KMWS_PROTO_OPCODE         2  /* opcode 3-7 or 11-15 */
+#define KMWS_PROTO_CONTROL        3  /* a control frame without FIN or longer than 125 bytes */
+#define KMWS_PROTO_CONTINUATION   4  /* CONTINUE with no open message */
+#define KMWS_PROTO_INTERLEAVED    5  /* opcode 1 or 2 while a message is open */
+#define KMWS_PROTO_CLOSE_PAYLOAD  6  /* CLOSE with one payload byte, or a status code outside
+                                        1000-1003, 1007-1014, 3000-4999 */
+#define KMWS_PROTO_CLOSE_REASON   7  /* CLOSE whose reason (bytes 2..) is not a complete well-formed UTF-8
+                                        string: answer 1007 */
+#define KMWS_PROTO_AFTER_CLOSE    8  /* any frame after a valid CLOSE */
+#define KMWS_PROTO_HEADER         9  /* err[i] != 0: the parser rejected the header */
+#define KMWS_PROTO_AFTER_FAIL     10 /* any frame after one of the above (this batch or, through the carry,
+                                        an earlier one) */
+
+/* State of one stream between two batches: all zero = IDLE; b[0] = the state
+ * (0 IDLE, 1 OPEN, 2 CLOSED, 3 FAILED), b[1..7] = 0. */
+typedef struct kmws_proto_carry { uint8_t b[8]; } kmws_proto_carry;
+
+/* Workspace bytes for kmws_proto_check: about 2 B per frame and 3 B per 1024
+ * frames or streams. */
+size_t kmws_proto_workspace_size(uint32_t n, uint32_t n_streams);
+
+/* Stream-ordered, no host sync, no allocation, three kernel nodes (capturable);
+ * the status word is cleared by a kernel.  The first rule that matches decides
+ * a frame's own class: err[i] != 0 -> HEADER; a forbidden RSV bit -> RSV; a
+ * reserved opcode -> OPCODE; a control frame without FIN or above 125 bytes ->
+ * CONTROL; a CLOSE body -> CLOSE_PAYLOAD / CLOSE_REASON.  Then, per stream in
+ * frame order: FAILED -> AFTER_FAIL; CLOSED -> AFTER_CLOSE; a nonzero class ->
+ * that class, FAILED; CONTINUE when IDLE -> CONTINUATION, FAILED; opcode 1 / 2
+ * when OPEN -> INTERLEAVED, FAILED; else OK, after which a CLOSE leaves CLOSED,
+ * PING / PONG change nothing and a data frame leaves IDLE with FIN, else OPEN.
+ *
+ * flags[i]: header byte 0 | mask << 8 (kmws_unpack_headers' out_flags); err
+ * (may be NULL: no frame has a header error): its out_err; descs[i].len: the
+ * payload length.  rsv_allowed: the RSV bits (0x40, 0x20, 0x10) allowed on a
+ * data message's head, e.g. 0x40 with permessage-deflate.  The descriptors
+ * need no order.  Only payloads of CLOSE frames with 2 <= len <= 125 and
+ * err == 0 are read, only in [off, off + len); one that reaches past span sets
+ * status bit 1 and is not read.  payload_masked, stream_first, n_streams,
+ * carry_in, carry_out: as kmws_utf8_validate's (NULL stream_first with
+ * n_streams == 1; an empty stream's carry_out equals its carry_in; a malformed
+ * array sets status bit 1); a carry_in whose b[0] is not 0..3 sets status bit 1.
+ * With status bit 1 set out / carry_out are not valid.  The payload is never
+ * written.  n == 0: KMWS_OK, carry_out = carry_in.  out: n bytes.
+ *
+ * KMWS_ERR_INVALID_PARAM: rsv_allowed & ~0x70, then kmws_utf8_validate's checks
+ * in its order (n or n_streams >= 2^31; with frames a NULL base, descs, flags,
+ * out or workspace; base not 16-byte aligned; no stream, or several without
+ * stream_first).  Then KMWS_ERR_BUFFER_TOO_SMALL below
+ * kmws_proto_workspace_size(n, n_streams) with frames, then
+ * KMWS_ERR_NOT_SUPPORTED without a gfx950 device: there is no CPU fallback
+ * (the host path's check, kmws_decoder_set_proto_check, needs no device).
+ *
+ * Cost: about 20 B read and 3 B written per frame; the lane that owns a CLOSE
+ * frame walks its at most 123 reason bytes serially while the 63 other lanes of
+ * its wave wait -- CLOSE frames are at most one per connection. */
+kmws_status kmws_proto_check(const uint8_t* base, uint64_t span, const kmws_desc* descs, const uint16_t* flags,
+                             const uint8_t* err, uint32_t n, int payload_masked, uint32_t rsv_allowed,
+                             const uint32_t* stream_first, uint32_t n_streams, const kmws_proto_carry* carry_in,
+                             kmws_proto_carry* carry_out, uint8_t* out, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ---- in-place unmask and UTF-8 validation in one pass over the payload ----
  * kmws_unmask_batch followed by kmws_utf8_validate reads every payload byte

@@ -730,6 +730,21 @@ public:
     // frame callback (kuma's FrameHeader has no spare field to carry it).
     int lastFrameUtf8() const { return st_->last_utf8; }
 
+    // kmws_decoder_set_proto_check: every frame is judged by RFC 6455's
+    // sequence and CLOSE rules (continuation order, reserved opcodes, RSV bits
+    // outside rsv_allowed -- 0x40 with permessage-deflate --, the CLOSE code and
+    // reason), on the host, with and without an RxLoop.  Off by default.
+    // Advisory: every frame is delivered as before; the application closes with
+    // 1002 when lastFrameProto() != KMWS_PROTO_OK, with 1007 when it is
+    // KMWS_PROTO_CLOSE_REASON.
+    void setProtocolCheck(bool on, unsigned rsv_allowed = 0)
+    {
+        if (st_->dec) kmws_decoder_set_proto_check(st_->dec, on ? 1 : 0, rsv_allowed);
+    }
+    // The KMWS_PROTO_* value of the frame being delivered: valid during the
+    // frame callback.
+    int lastFrameProto() const { return st_->last_proto; }
+
     void setFrameCallback(FrameCallback cb) { st_->cb = std::move(cb); }  // WSHandler.h:46
 
     void reset()  // WSHandler.cpp:324-327
@@ -832,6 +847,7 @@ private:
             h.length = k->length;
             Buffer view(static_cast<void*>(payload), len, len);
             s->last_utf8 = kmws_frame_utf8(k);
+            s->last_proto = kmws_decoder_frame_proto(s->dec);
             if (s->cb) {
                 FrameCallback cb = s->cb;  // the callback may replace or drop itself
                 (void)cb(h, view);
@@ -845,6 +861,7 @@ private:
         bool alive = true;
         int last_status = KMWS_OK;
         int last_utf8 = KMWS_UTF8_NOT_TEXT;  // kmws_frame_hdr.reserved of the frame being delivered
+        int last_proto = KMWS_PROTO_OK;      // kmws_decoder_frame_proto of the frame being delivered
         RxLoop* rx = nullptr;
     };
     std::shared_ptr<State> st_;

@@ -16,6 +16,10 @@
 // UTF-8 message state (kmws_utf8_stream.hpp), the payload pass validates the
 // bytes of checked frames while it unmasks them, and the verdict is delivered
 // in kmws_frame_hdr.reserved.  With the check off nothing here changes.
+// kmws_decoder_set_proto_check (opt-in): the parser judges each completed frame
+// by the sequence and CLOSE rules (kmws_proto_stream.hpp; no GPU), the verdict
+// waits with the queued frame and is published on the decoder while the
+// frame's callback runs (kmws_decoder_frame_proto).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -28,6 +32,7 @@
 
 #include "kmws_gpu.h"
 #include "kmws_host_util.hpp"
+#include "kmws_proto_stream.hpp"
 #include "kmws_utf8_stream.hpp"
 
 using namespace kmws;
@@ -57,6 +62,7 @@ struct Pending {
     Origin where;
     Utf8StreamView uv;  // kmws_decoder_set_utf8_check: the frame's view (w == 0: not checked)
     uint32_t slot;      // its verdict byte in the stage (kNoSlot: empty or unchecked, no device work)
+    uint8_t proto;      // kmws_decoder_set_proto_check: the frame's KMWS_PROTO_* value (0 with the check off)
 };
 
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
@@ -95,6 +101,11 @@ struct kmws_decoder {
     // and only for items that are still live.
     bool utf8_check = false;
     Utf8Stream utf8;
+    // kmws_decoder_set_proto_check.  The state advances in the feeds' sinks
+    // (frame_facts); frame_proto holds a frame's verdict while its callback runs.
+    bool proto_check = false;
+    ProtoStream proto;
+    int frame_proto = KMWS_PROTO_OK;
 
     // What both feeds derive from a completed frame whose payload lies
     // contiguous (and still masked) at `payload`.
@@ -104,6 +115,7 @@ struct kmws_decoder {
         uint32_t key;
         uint32_t dkey;      // its descriptor's key; 0 when unmasked: checked, not stored
         Utf8StreamView uv;  // the frame's view from the parse-time half, which advances here (w == 0: not checked)
+        uint8_t proto;      // the frame's KMWS_PROTO_* value; the stream's state advances here too
         bool gpu() const { return masked || checked; }
     };
     Facts frame_facts(const kmws_frame_hdr& h, const uint8_t* payload)
@@ -118,6 +130,8 @@ struct kmws_decoder {
             f.uv = utf8_stream_frame(utf8, op_byte_of(h), tail, nb);
         }
         f.checked = (f.uv.w & kUtf8Checked) != 0u && h.length;
+        if (proto_check)
+            f.proto = (uint8_t)proto_stream_frame(proto, op_byte_of(h), payload, h.length, h.mask ? f.key : 0u);
         return f;
     }
 
@@ -265,6 +279,7 @@ struct RxItem {
     bool live;        // false once discarded
     Utf8StreamView uv;  // the frame's view from the parse-time half (w == 0: not checked)
     uint32_t slot;      // its verdict byte in the generation's stage (kNoSlot: none)
+    uint8_t proto;      // the frame's KMWS_PROTO_* value, published on `dec` around its callback (live items only)
 };
 // One submitted generation: its frames, and the pinned stage that holds
 // their staged payloads and the unmask launch in flight.
@@ -591,7 +606,19 @@ void kmws_decoder_reset(kmws_decoder* dec)
     if (!dec) return;
     dec->reset_ctx();
     utf8_stream_reset(dec->utf8);  // between messages again
+    proto_stream_reset(dec->proto);
 }
+
+void kmws_decoder_set_proto_check(kmws_decoder* dec, int on, uint32_t rsv_allowed)
+{
+    if (!dec) return;
+    const bool want = on != 0;
+    if (want != dec->proto_check) proto_stream_reset(dec->proto);
+    dec->proto_check = want;
+    dec->proto.rsv_allowed = (uint8_t)(rsv_allowed & 0x70u);
+}
+
+int kmws_decoder_frame_proto(const kmws_decoder* dec) { return dec ? dec->frame_proto : KMWS_PROTO_OK; }
 
 void kmws_decoder_set_utf8_check(kmws_decoder* dec, int on)
 {
@@ -634,7 +661,7 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
         // A frame with payload that is masked or checked goes to the GPU (key
         // 0 when unmasked: checked, not stored).
         const kmws_decoder::Facts f = dec->frame_facts(h, payload);
-        dec->pending.push_back(Pending{h, nullptr, 0, 0, kInChunk, f.uv, kNoSlot});
+        dec->pending.push_back(Pending{h, nullptr, 0, 0, kInChunk, f.uv, kNoSlot, f.proto});
         Pending& qq = dec->pending.back();  // from here on the frame counts as parsed: a failure below drops it
         if (f.gpu() && !bs.get()) return bs.st;
         auto stage_payload = [&]() -> kmws_status {
@@ -726,7 +753,11 @@ int kmws_decoder_feed(kmws_decoder* dec, uint8_t* data, size_t len, kmws_frame_c
         }
         // WSHandler::handleFrame (:282-289): a callback that destroyed its
         // owner ends the call; the decoder must not be touched afterwards.
+        // the decoder is alive until a callback says otherwise: the verdict is
+        // published for the callback and cleared behind it
+        dec->frame_proto = q.proto;
         if (cb && cb(&q.hdr, payload, q.hdr.length, user)) return KMWS_WS_DESTROYED;
+        dec->frame_proto = KMWS_PROTO_OK;
     }
     return result;
 }
@@ -998,7 +1029,7 @@ int kmws_decoder_feed_deferred(kmws_decoder* dec, kmws_rx_batch* b, const uint8_
         if (f.masked) b->pending_bytes += h.length;
         // queued first: a frame the parse-time half has seen must be dropped
         // through rx_drop_utf8 if its payload cannot be staged
-        b->items.push_back(RxItem{dec, cb, user, h, 0, nullptr, true, f.uv, kNoSlot});
+        b->items.push_back(RxItem{dec, cb, user, h, 0, nullptr, true, f.uv, kNoSlot, f.proto});
         RxItem& it = b->items.back();
         if (!reasm && b->ring.holds(payload, h.length)) {
             // payload lies in the caller's pinned ring: unmasked there, no copy
@@ -1122,7 +1153,11 @@ int kmws_rx_batch_poll(kmws_rx_batch* b, int wait)
             // "destroyed" (WSHandler.cpp:284-287): none of that decoder's frames
             // may reach its callback again -- the rest of this generation, every
             // later generation in flight and the one still being fed
+            // a live item's decoder is alive (see RxItem::dec); after the callback
+            // it is touched again only if the item is still live
+            it.dec->frame_proto = it.proto;
             if (it.cb && it.cb(&it.hdr, payload, it.hdr.length, it.user)) kmws_rx_batch_discard(b, it.dec);
+            if (it.live) it.dec->frame_proto = KMWS_PROTO_OK;
         }
         b->delivering = nullptr;
         b->flushing = false;

@@ -67,28 +67,6 @@ __device__ __forceinline__ Utf8Elem block_scan(Utf8Elem e, Utf8Elem* s)
     return s[tid];
 }
 
-// The stream of frame i: the last s in [0, ns) with first[s] <= i (empty streams
-// before it share its start and lose).  Every index stays in range whatever the
-// array holds.  first == nullptr: one stream.
-__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ first, uint32_t ns, uint32_t i)
-{
-    if (!first) return 0u;
-    uint32_t lo = 0, hi = ns - 1;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (first[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint32_t stream_begin(const uint32_t* __restrict__ first, uint32_t s)
-{
-    return first ? first[s] : 0u;
-}
-__device__ __forceinline__ uint32_t stream_end(const uint32_t* __restrict__ first, uint32_t n, uint32_t s)
-{
-    return first ? first[s + 1] : n;
-}
-
 // kmws_utf8_carry has byte alignment: read and written byte by byte.
 __device__ __forceinline__ uint64_t load_carry(const kmws_utf8_carry* __restrict__ c, uint32_t s)
 {

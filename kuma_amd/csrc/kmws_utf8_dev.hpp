@@ -62,6 +62,28 @@ __device__ __forceinline__ void report_bad(uint32_t* __restrict__ first_bad, uin
     if (__builtin_nontemporal_load(&first_bad[slot]) > frame + 1u) atomicMin(&first_bad[slot], frame + 1u);
 }
 
+// The stream of frame i: the last s in [0, ns) with first[s] <= i (empty streams
+// before it share its start and lose).  Every index stays in range whatever the
+// array holds.  first == nullptr: one stream.
+__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ first, uint32_t ns, uint32_t i)
+{
+    if (!first) return 0u;
+    uint32_t lo = 0, hi = ns - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (first[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint32_t stream_begin(const uint32_t* __restrict__ first, uint32_t s)
+{
+    return first ? first[s] : 0u;
+}
+__device__ __forceinline__ uint32_t stream_end(const uint32_t* __restrict__ first, uint32_t n, uint32_t s)
+{
+    return first ? first[s + 1] : n;
+}
+
 // ---- the per-frame kernels around a payload pass of another file ----
 // `fa`: where the frame arrays lie in `workspace` (kmws_workspace.hpp), whose
 // WsHead holds the status word.  launch_utf8_frame_state runs utf8_elem_kernel, utf8_scan_aggs_kernel and

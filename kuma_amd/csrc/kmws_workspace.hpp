@@ -8,7 +8,7 @@
 //   copy = head | tile prefixes + totals | row prefixes | unit form: edge words | unit records
 //                                                       | chunk form: chunk map | dense list
 //   reframe = copy | outgoing flags     gather_utf8 = copy | frame arrays     reframe_utf8 = reframe | frame arrays
-//   pack_headers = head | tile states
+//   pack_headers = head | tile states     proto = head | block aggregates | their prefixes | per-frame bytes
 // The one alias: the copy's edge words and its chunk map start at the same
 // offset (edge == cmap); a batch takes one form (copy_uses_chunks), only that
 // form's regions are live and the other's counts are 0.  Inside one region: the
@@ -16,6 +16,7 @@
 // row prefixes, and the frame arrays' elements become the frames' views in place.
 #pragma once
 #include "kmws_common.hpp"
+#include "kmws_proto_rule.hpp"
 
 namespace kmws {
 
@@ -149,6 +150,30 @@ inline CopyFamilyWs copy_family_ws(uint32_t n, uint64_t cap, bool reframe, bool 
 inline CopyFamilyWs reframe_ws(uint32_t n, uint64_t cap) { return copy_family_ws(n, cap, true, false, 0); }
 inline CopyFamilyWs gather_utf8_ws(uint32_t n, uint64_t cap, uint32_t ns) { return copy_family_ws(n, cap, false, true, ns); }
 inline CopyFamilyWs reframe_utf8_ws(uint32_t n, uint64_t cap, uint32_t ns) { return copy_family_ws(n, cap, true, true, ns); }
+
+// kmws_proto_check: head | uint16_t aggs[nagg] | uint8_t pre[nagg] | uint8_t local[nblk * F]
+// | uint8_t incl[nblk * F], F = kProtoBlockFrames.  nblk blocks hold frames; the
+// element pass also runs over the n_streams + 1 entries of stream_first, so nagg
+// = the blocks of the longer of the two, each with an aggregate (the block's
+// state function, its status bits above it) and a scanned prefix.  The frame
+// arrays cover whole blocks: a lane stores its four frames' bytes as one word.
+struct ProtoWs {
+    uint32_t nblk, nagg;
+    uint64_t aggs, pre, local, incl, total;
+};
+inline ProtoWs proto_ws(uint32_t n, uint32_t n_streams)
+{
+    ProtoWs w{};
+    w.nblk = (uint32_t)ceil_div(n, kProtoBlockFrames);
+    const uint32_t sblk = (uint32_t)ceil_div((uint64_t)n_streams + 1, kProtoBlockFrames);
+    w.nagg = w.nblk > sblk ? w.nblk : sblk;
+    w.aggs = r16(sizeof(WsHead));
+    w.pre = w.aggs + r16((uint64_t)w.nagg * 2);
+    w.local = w.pre + r16((uint64_t)w.nagg);
+    w.incl = w.local + (uint64_t)w.nblk * kProtoBlockFrames;
+    w.total = w.incl + (uint64_t)w.nblk * kProtoBlockFrames;
+    return w;
+}
 
 // kmws_pack_headers with wire offsets: head | uint64_t states[nt], one per scan
 // tile; the kernel's front zeroes all of it, total / 8 words.

@@ -53,9 +53,13 @@ EXPORTS = [
     "kmws_gather_utf8_workspace_size", "kmws_gather_unmask_utf8", "kmws_unpack_gather_utf8",
     "kmws_reframe_workspace_size", "kmws_reframe_batch", "kmws_unpack_reframe",
     "kmws_reframe_utf8_workspace_size", "kmws_reframe_utf8_batch", "kmws_unpack_reframe_utf8",
+    "kmws_proto_workspace_size", "kmws_proto_check", "kmws_decoder_set_proto_check", "kmws_decoder_frame_proto",
 ]
 # per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
 UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
+# per-frame results of kmws_proto_check / kmws_decoder_frame_proto (include/kmws_gpu.h KMWS_PROTO_*)
+PROTO_OK, PROTO_RSV, PROTO_OPCODE, PROTO_CONTROL, PROTO_CONTINUATION, PROTO_INTERLEAVED = 0, 1, 2, 3, 4, 5
+PROTO_CLOSE_PAYLOAD, PROTO_CLOSE_REASON, PROTO_AFTER_CLOSE, PROTO_HEADER, PROTO_AFTER_FAIL = 6, 7, 8, 9, 10
 #: every function include/kmws_bench.h declares (bench / test support, same library)
 BENCH_EXPORTS = [
     "kmws_arena_alloc", "kmws_arena_free", "kmws_arena_place", "kmws_fill_synthetic", "kmws_fill_uniform_descs",
@@ -132,6 +136,8 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_decoder_set_in_place": (None, [vp, i32]),
         "kmws_decoder_set_utf8_check": (None, [vp, i32]),
         "kmws_frame_utf8": (C.c_uint8, [C.POINTER(FrameHdr)]),
+        "kmws_decoder_set_proto_check": (None, [vp, i32, u32]),
+        "kmws_decoder_frame_proto": (i32, [vp]),
         "kmws_decoder_feed": (i32, [vp, u8p, sz, FRAME_CB, vp]),
         "kmws_device_count": (i32, []),
         "kmws_unmask_workspace_size": (sz, [u64]),
@@ -203,6 +209,8 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_device_numa_node": (i32, [i32, C.POINTER(C.c_int)]),
         "kmws_utf8_workspace_size": (sz, [u64, u32, u32]),
         "kmws_utf8_validate": (i32, [u8p, u64, vp, vp, u32, i32, vp, u32, vp, vp, u8p, vp, sz, vp]),
+        "kmws_proto_workspace_size": (sz, [u32, u32]),
+        "kmws_proto_check": (i32, [u8p, u64, vp, vp, vp, u32, i32, u32, vp, u32, vp, vp, u8p, vp, sz, vp]),
         "kmws_unmask_utf8_workspace_size": (sz, [u64, u32, u32]),
         "kmws_unmask_utf8_batch": (i32, [u8p, u64, vp, vp, u32, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
         "kmws_unpack_unmask_utf8": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
@@ -355,6 +363,19 @@ class WSHandler:
         """kmws_decoder_set_utf8_check (default off): the callback's Header.utf8
         holds UTF8_NOT_TEXT / OK / BAD / AFTER_BAD.  Switch between messages only."""
         lib().kmws_decoder_set_utf8_check(self._d, int(bool(on)))
+
+    def set_proto_check(self, on: bool, rsv_allowed: int = 0) -> None:
+        """kmws_decoder_set_proto_check (default off): RFC 6455's sequence and CLOSE
+        rules, judged on the host; rsv_allowed: the RSV bits (0x40, 0x20, 0x10) a
+        data message's head may carry."""
+        lib().kmws_decoder_set_proto_check(self._d, int(bool(on)), rsv_allowed)
+
+    def last_frame_proto(self) -> int:
+        """kmws_decoder_frame_proto: the PROTO_* value of the frame whose callback
+        is running; 0 outside one or with the check off."""
+        return lib().kmws_decoder_frame_proto(self._d)
+
+    setProtocolCheck, lastFrameProto = set_proto_check, last_frame_proto  # include/kmws_wshandler.hpp's names
 
     def handleData(self, data) -> int:
         n = len(data)
@@ -950,6 +971,39 @@ def utf8_validate(base, descs, flags, out, ws: Workspace, span: Optional[int] = 
 
 def _opt(t):
     return t.data_ptr() if t is not None else None
+
+
+def proto_workspace_size(n: int, n_streams: int = 1) -> int:
+    return lib().kmws_proto_workspace_size(n, n_streams)
+
+
+def proto_check(base, descs, flags, out, ws: Workspace, err=None, span: Optional[int] = None, masked: bool = False,
+                rsv_allowed: int = 0, stream_first=None, carry_in=None, carry_out=None, stream=None) -> None:
+    """kmws_proto_check (stream-ordered): out (uint8, n) receives PROTO_OK ..
+    PROTO_AFTER_FAIL per frame; base is only read, and only under CLOSE frames.
+    descs (n, 2) int64, flags int16 (n,), err uint8 (n,) or None as
+    unpack_headers writes them; masked: the payload bytes are still masked with
+    the descriptors' keys; rsv_allowed: RSV bits (0x40, 0x20, 0x10) allowed on a
+    data head.  stream_first / carry_in / carry_out as utf8_validate's (a carry's
+    first byte is the stream's state, 0..3).  ws: proto_workspace_size(n,
+    n_streams).  out and carry_out are valid only when the workspace status is 0
+    afterwards."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(base, "base", 1, dev)
+    _check_tensor(flags, "flags", 2, dev, n)
+    if err is not None:
+        _check_tensor(err, "err", 1, dev, n)
+    _check_tensor(out, "out", 1, dev, n)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = _check_streams(stream_first, carry_in, carry_out, dev)
+    span = base.numel() if span is None else span
+    if span > base.numel():
+        raise ValueError(f"span {span} exceeds base ({base.numel()} bytes)")
+    _check(lib().kmws_proto_check(base.data_ptr(), span, descs.data_ptr(), flags.data_ptr(), _opt(err), n,
+                                  int(bool(masked)), rsv_allowed, _opt(stream_first), ns, _opt(carry_in),
+                                  _opt(carry_out), out.data_ptr(), ws.ptr, ws.nbytes, _stream_handle(stream)),
+           "kmws_proto_check")
 
 
 def unpack_unmask(wire, hdr_off, mode: int, out_desc, out_flags, out_err, ws: Workspace,
