@@ -558,7 +558,16 @@ kmws_status kmws_find_headers(const uint8_t* wire, uint64_t len, uint64_t* hdr_o
  * into wire) go to hdr_off[s * cap .. s * cap + n_out[s]); consumed[s] (may be
  * NULL) = bytes of stream s covered by its complete frames.  Stopping rules as
  * kmws_find_headers: cap frames, a truncated frame or invalid length (recorded),
- * or after a CLOSE frame.  All pointers device memory. */
+ * or after a CLOSE frame.  All pointers device memory.
+ * A stream's last recorded frame was recorded without being consumed -- cut by
+ * the stream's end, or refused for its length: the outputs do not say which --
+ * iff its offset equals stream_off[s] + consumed[s].  Leave that one out of the
+ * flat hdr_off list the kmws_unpack_* entries take: they bound a frame's header
+ * bytes by wire_len only, so a cut header in front of another stream's bytes
+ * would be completed with them.  Parse it alone instead (kmws_unpack_headers,
+ * n = 1, wire_len = the stream's end): out_err 1 means wait for the next read,
+ * anything else fails the connection ("The receive
+ * loop of a device batch"; tests/test_gpu_server_loop.py). */
 kmws_status kmws_find_headers_streams(const uint8_t* wire, uint64_t wire_len, const uint64_t* stream_off,
                                       uint32_t n_streams, uint64_t* hdr_off, uint32_t cap, uint32_t* n_out,
                                       uint64_t* consumed, void* stream);
