@@ -710,6 +710,103 @@ kmws_status kmws_proto_check(const uint8_t* base, uint64_t span, const kmws_desc
                              kmws_proto_carry* carry_out, uint8_t* out, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* ---- the message table of a device batch (opt-in) ----
+ * The entries above leave per-frame arrays; an application consumes messages.
+ * kuma hands fragments up with their FIN flag (data_cb_(buf, is_text, fin)) and
+ * lets the application put the message together; behind a device batch that is
+ * a serial host walk over every stream's frames.  This call does it on the
+ * device: one record per message, in frame order, with where its payload lies,
+ * how long it is and whether it may be delivered.  Nothing else changes
+ * behaviour; no payload byte is read or written. */
+#define KMWS_MSG_NONE   0xFFFFFFFFu  /* msg_of[i] of a control frame or an orphan CONTINUE */
+#define KMWS_MSG_BEGIN  1u  /* the message's head is in this batch */
+#define KMWS_MSG_END    2u  /* its FIN frame is in this batch */
+#define KMWS_MSG_CONTIG 4u  /* pos[last] + len[last] - pos[first] == bytes: its members' payloads
+                               are one run at `off` (always so for a one-frame message) */
+typedef struct kmws_msg {            /* 48 B */
+    uint64_t off;     /* pos[first] */
+    uint64_t bytes;   /* payload bytes of its members in this batch */
+    uint64_t prior;   /* its payload bytes in earlier batches (from the carry; 0 with BEGIN) */
+    uint32_t stream, first, last, frames;   /* first / last member frame index, member count */
+    uint8_t  b0;      /* head byte 0 & 0x7F (RSV1-3, opcode), from the carry when continued */
+    uint8_t  bits;    /* KMWS_MSG_* */
+    uint8_t  utf8;    /* utf8[last]  (0 when utf8  == NULL) */
+    uint8_t  proto;   /* proto[last] (0 when proto == NULL) */
+    uint32_t reserved;  /* 0 */
+} kmws_msg;
+/* State of one stream between two batches: all zero = no message open; b[0] = 0x80 | b0,
+ * b[1..7] = 0, b[8..15] = prior + bytes of the open message, little endian. */
+typedef struct kmws_msg_carry { uint8_t b[16]; } kmws_msg_carry;
+
+/* Workspace bytes for kmws_msg_index: 2 B per frame (whole blocks of 1024) and
+ * 56 B per 1024 frames or 8 B per 1024 streams, whichever blocks are more. */
+size_t kmws_msg_workspace_size(uint32_t n, uint32_t n_streams);
+
+/* Stream-ordered, no host sync, no allocation, five kernel nodes (capturable);
+ * the status word is stored by a kernel.  kmws_utf8_validate's message rule,
+ * per stream in frame order: a control frame (opcode >= 8) is no member and
+ * does not touch the state; opcode 1-7 (a head) starts a message, replacing an
+ * unfinished one, which keeps its record without END (whether that is an error
+ * is kmws_proto_check's business), and is its first member; opcode 0 while a
+ * message is open is a member, and starts the record when it is the message's
+ * first member in this batch (the message is open through the carry: b0 and
+ * prior come from carry_in); opcode 0 while none is open is an orphan: no
+ * member, the state unchanged; FIN on a member closes the message.  A frame
+ * whose header failed to parse arrives as the kmws_unpack_* entries leave it
+ * (len 0, flags as parsed) and is treated by its flags like any other; the
+ * caller sees it through the proto verdict (HEADER, then AFTER_FAIL, sticky).
+ *
+ * flags[i]: header byte 0 | mask << 8 (kmws_unpack_headers' out_flags);
+ * descs[i].len: the payload length -- nothing else of a descriptor is used
+ * unless pos == NULL.  pos: n entries, frame i's payload position in whatever
+ * arena the caller will read -- the dst_off of a gather -- or NULL:
+ * descs[i].off.  utf8 / proto: the out arrays of kmws_utf8_validate (or a
+ * fused payload pass) and kmws_proto_check, or NULL; both kinds of verdict are
+ * sticky within a message or stream, so a record carries its last member's
+ * values and no reduction is made.  stream_first, n_streams, carry_in,
+ * carry_out: as kmws_proto_check's (NULL stream_first with n_streams == 1; an
+ * empty stream's carry_out equals its carry_in, and so does that of a stream
+ * without a member in this batch; a malformed array sets status bit 1), with
+ * kmws_msg_carry entries, which have byte alignment; a carry_in with b[0] in
+ * 1..0x7F or a nonzero b[1..7] sets status bit 1.
+ *
+ * Records come out in frame order of their first member, and so grouped by
+ * stream: msgs[0 .. *msg_count), at most msg_cap (n always suffices); msgs is
+ * 8-byte aligned.  stream_msg_first (n_streams + 1 entries, may be NULL): the
+ * number of records before each stream, [n_streams] == *msg_count.  msg_of (n
+ * entries, may be NULL): each frame's record index, or KMWS_MSG_NONE.  A
+ * message without CONTIG has a control frame with payload between its
+ * fragments (or positions that are not dense): read its members through
+ * msg_of / pos.  More records than msg_cap: status bit 1 is set, *msg_count
+ * holds the needed number, and msgs, msg_of and carry_out are not valid; they
+ * are not valid either when status bit 1 is set for another reason.  n == 0:
+ * KMWS_OK, *msg_count = 0, stream_msg_first all 0, carry_out = carry_in; the
+ * workspace is not touched.
+ *
+ * KMWS_ERR_INVALID_PARAM: n or n_streams >= 2^31; a NULL msg_count or
+ * workspace; with frames a NULL descs, flags or msgs; with frames no stream, or
+ * several without stream_first.  Then KMWS_ERR_BUFFER_TOO_SMALL below
+ * kmws_msg_workspace_size(n, n_streams) with frames, then
+ * KMWS_ERR_NOT_SUPPORTED without a gfx950 device: there is no CPU fallback.
+ *
+ * Not done: a gather that leaves control payloads out so that every message is
+ * contiguous (CONTIG reports the case); a message size limit (prior + bytes is
+ * what a caller needs for 1009); a host-path assembler (the drop-in keeps
+ * kuma's per-frame callbacks).
+ *
+ * carry_out must not overlap carry_in.
+ *
+ * Cost: three passes over the frames that read 2, 2 + 4 and 2 + 4 B per frame
+ * (flags, and the members' lengths out of their 16-byte descriptors), 2 B per
+ * frame stored to and reloaded from the workspace, 4 B per frame stored for
+ * msg_of, and per message 48 B stored after about 30 B of gathered reads. */
+kmws_status kmws_msg_index(const kmws_desc* descs, const uint16_t* flags, const uint64_t* pos,
+                           const uint8_t* utf8, const uint8_t* proto, uint32_t n,
+                           const uint32_t* stream_first, uint32_t n_streams,
+                           const kmws_msg_carry* carry_in, kmws_msg_carry* carry_out,
+                           uint32_t* msg_of, kmws_msg* msgs, uint32_t msg_cap, uint32_t* msg_count,
+                           uint32_t* stream_msg_first, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- in-place unmask and UTF-8 validation in one pass over the payload ----
  * kmws_unmask_batch followed by kmws_utf8_validate reads every payload byte
  * twice; these entries read it once: the words the unmask stores are validated

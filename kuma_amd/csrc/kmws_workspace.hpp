@@ -9,6 +9,7 @@
 //                                                       | chunk form: chunk map | dense list
 //   reframe = copy | outgoing flags     gather_utf8 = copy | frame arrays     reframe_utf8 = reframe | frame arrays
 //   pack_headers = head | tile states     proto = head | block aggregates | their prefixes | per-frame bytes
+//   msg = head | state aggregates | their prefixes | sum aggregates | their prefixes + total | per-frame words
 // The one alias: the copy's edge words and its chunk map start at the same
 // offset (edge == cmap); a batch takes one form (copy_uses_chunks), only that
 // form's regions are live and the other's counts are 0.  Inside one region: the
@@ -16,6 +17,7 @@
 // row prefixes, and the frame arrays' elements become the frames' views in place.
 #pragma once
 #include "kmws_common.hpp"
+#include "kmws_msg_rule.hpp"
 #include "kmws_proto_rule.hpp"
 
 namespace kmws {
@@ -172,6 +174,32 @@ inline ProtoWs proto_ws(uint32_t n, uint32_t n_streams)
     w.local = w.pre + r16((uint64_t)w.nagg);
     w.incl = w.local + (uint64_t)w.nblk * kProtoBlockFrames;
     w.total = w.incl + (uint64_t)w.nblk * kProtoBlockFrames;
+    return w;
+}
+
+// kmws_msg_index: head | uint32_t aggs_a[nagg] | uint32_t pre_a[nagg] | MsgSum aggs_b[nblk]
+// | MsgSum pre_b[nblk + 1] | uint16_t cls[nblk * F], F = kMsgBlockFrames.  nblk blocks
+// hold frames; the first pass also runs over the n_streams + 1 entries of
+// stream_first, so nagg = the blocks of the longer of the two (scan A: a block's
+// state function, its status bits above it).  Scan B has an aggregate per block of
+// frames, and its prefixes end with the batch's total.  cls covers whole blocks: a
+// lane stores its four frames' words as one.
+struct MsgWs {
+    uint32_t nblk, nagg;
+    uint64_t aggs_a, pre_a, aggs_b, pre_b, cls, total;
+};
+inline MsgWs msg_ws(uint32_t n, uint32_t n_streams)
+{
+    MsgWs w{};
+    w.nblk = (uint32_t)ceil_div(n, kMsgBlockFrames);
+    const uint32_t sblk = (uint32_t)ceil_div((uint64_t)n_streams + 1, kMsgBlockFrames);
+    w.nagg = w.nblk > sblk ? w.nblk : sblk;
+    w.aggs_a = r16(sizeof(WsHead));
+    w.pre_a = w.aggs_a + r16((uint64_t)w.nagg * 4);
+    w.aggs_b = w.pre_a + r16((uint64_t)w.nagg * 4);
+    w.pre_b = w.aggs_b + r16((uint64_t)w.nblk * sizeof(MsgSum));
+    w.cls = w.pre_b + r16(((uint64_t)w.nblk + 1) * sizeof(MsgSum));
+    w.total = w.cls + (uint64_t)w.nblk * kMsgBlockFrames * 2;
     return w;
 }
 

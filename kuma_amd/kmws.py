@@ -54,12 +54,16 @@ EXPORTS = [
     "kmws_reframe_workspace_size", "kmws_reframe_batch", "kmws_unpack_reframe",
     "kmws_reframe_utf8_workspace_size", "kmws_reframe_utf8_batch", "kmws_unpack_reframe_utf8",
     "kmws_proto_workspace_size", "kmws_proto_check", "kmws_decoder_set_proto_check", "kmws_decoder_frame_proto",
+    "kmws_msg_workspace_size", "kmws_msg_index",
 ]
 # per-frame results of kmws_utf8_validate (include/kmws_gpu.h KMWS_UTF8_*)
 UTF8_NOT_TEXT, UTF8_OK, UTF8_BAD, UTF8_AFTER_BAD = 0, 1, 2, 3
 # per-frame results of kmws_proto_check / kmws_decoder_frame_proto (include/kmws_gpu.h KMWS_PROTO_*)
 PROTO_OK, PROTO_RSV, PROTO_OPCODE, PROTO_CONTROL, PROTO_CONTINUATION, PROTO_INTERLEAVED = 0, 1, 2, 3, 4, 5
 PROTO_CLOSE_PAYLOAD, PROTO_CLOSE_REASON, PROTO_AFTER_CLOSE, PROTO_HEADER, PROTO_AFTER_FAIL = 6, 7, 8, 9, 10
+# kmws_msg_index (include/kmws_gpu.h KMWS_MSG_*): msg_of of a frame in no message; the bits of a record
+MSG_NONE = 0xFFFFFFFF
+MSG_BEGIN, MSG_END, MSG_CONTIG = 1, 2, 4
 #: every function include/kmws_bench.h declares (bench / test support, same library)
 BENCH_EXPORTS = [
     "kmws_arena_alloc", "kmws_arena_free", "kmws_arena_place", "kmws_fill_synthetic", "kmws_fill_uniform_descs",
@@ -82,6 +86,21 @@ class FrameHdr(C.Structure):
                 ("opcode", C.c_uint8), ("mask", C.c_uint8), ("plen", C.c_uint8),
                 ("reserved", C.c_uint8), ("xpl64", C.c_uint64), ("maskey", C.c_uint8 * 4),
                 ("length", C.c_uint32)]
+
+
+class Msg(C.Structure):
+    """kmws_msg: one record of kmws_msg_index, 48 bytes."""
+    _fields_ = [("off", C.c_uint64), ("bytes", C.c_uint64), ("prior", C.c_uint64), ("stream", C.c_uint32),
+                ("first", C.c_uint32), ("last", C.c_uint32), ("frames", C.c_uint32), ("b0", C.c_uint8),
+                ("bits", C.c_uint8), ("utf8", C.c_uint8), ("proto", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+def msg_dtype():
+    """The numpy dtype of the same 48 bytes: msgs.cpu().numpy().view(msg_dtype())."""
+    import numpy as np
+    return np.dtype([("off", "<u8"), ("bytes", "<u8"), ("prior", "<u8"), ("stream", "<u4"), ("first", "<u4"),
+                     ("last", "<u4"), ("frames", "<u4"), ("b0", "u1"), ("bits", "u1"), ("utf8", "u1"),
+                     ("proto", "u1"), ("reserved", "<u4")])
 
 
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.POINTER(FrameHdr), C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p)
@@ -211,6 +230,8 @@ def bind(L: C.CDLL) -> C.CDLL:
         "kmws_utf8_validate": (i32, [u8p, u64, vp, vp, u32, i32, vp, u32, vp, vp, u8p, vp, sz, vp]),
         "kmws_proto_workspace_size": (sz, [u32, u32]),
         "kmws_proto_check": (i32, [u8p, u64, vp, vp, vp, u32, i32, u32, vp, u32, vp, vp, u8p, vp, sz, vp]),
+        "kmws_msg_workspace_size": (sz, [u32, u32]),
+        "kmws_msg_index": (i32, [vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, sz, vp]),
         "kmws_unmask_utf8_workspace_size": (sz, [u64, u32, u32]),
         "kmws_unmask_utf8_batch": (i32, [u8p, u64, vp, vp, u32, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
         "kmws_unpack_unmask_utf8": (i32, [u8p, u64, vp, u32, i32, vp, vp, vp, vp, u32, vp, vp, u8p, vp, sz, i32, vp]),
@@ -1004,6 +1025,46 @@ def proto_check(base, descs, flags, out, ws: Workspace, err=None, span: Optional
                                   int(bool(masked)), rsv_allowed, _opt(stream_first), ns, _opt(carry_in),
                                   _opt(carry_out), out.data_ptr(), ws.ptr, ws.nbytes, _stream_handle(stream)),
            "kmws_proto_check")
+
+
+def msg_workspace_size(n: int, n_streams: int = 1) -> int:
+    return lib().kmws_msg_workspace_size(n, n_streams)
+
+
+def msg_index(descs, flags, msgs, msg_count, ws: Workspace, pos=None, utf8=None, proto=None, stream_first=None,
+              carry_in=None, carry_out=None, msg_of=None, stream_msg_first=None, msg_cap: Optional[int] = None,
+              stream=None) -> None:
+    """kmws_msg_index (stream-ordered): msgs (uint8, 48 * msg_cap; view it with
+    msg_dtype()) receives one record per message in frame order and msg_count
+    (int32, 1) their number.  descs (n, 2) int64 and flags int16 (n,) as
+    unpack_headers writes them; pos int64 (n,): the payload positions, e.g. a
+    gather's dst_off (None: the descriptors' offsets); utf8 / proto uint8 (n,):
+    the verdict arrays of the checks, or None.  stream_first as utf8_validate's;
+    carry_in / carry_out: uint8 (n_streams, 16); msg_of int32 (n,) and
+    stream_msg_first int32 (n_streams + 1,) or None.  msg_cap: records msgs
+    holds (default: all of it).  ws: msg_workspace_size(n, n_streams).  The
+    outputs are valid only when the workspace status is 0 afterwards; with bit 1
+    set for too small a msg_cap, msg_count holds the number needed."""
+    n = _check_descs(descs)
+    dev = descs.device
+    _check_tensor(flags, "flags", 2, dev, n)
+    cap = msgs.numel() // C.sizeof(Msg) if msg_cap is None else msg_cap
+    _check_tensor(msgs, "msgs", 1, dev, cap * C.sizeof(Msg))
+    _check_tensor(msg_count, "msg_count", 4, dev, 1)
+    _check_tensor(ws.tensor, "workspace", 1, dev)
+    ns = 1
+    if stream_first is not None:
+        _check_tensor(stream_first, "stream_first", 4, dev, 2)
+        ns = stream_first.numel() - 1
+    for name, t, elem, count in (("pos", pos, 8, n), ("utf8", utf8, 1, n), ("proto", proto, 1, n),
+                                 ("carry_in", carry_in, 1, 16 * ns), ("carry_out", carry_out, 1, 16 * ns),
+                                 ("msg_of", msg_of, 4, n), ("stream_msg_first", stream_msg_first, 4, ns + 1)):
+        if t is not None:
+            _check_tensor(t, name, elem, dev, count)
+    _check(lib().kmws_msg_index(descs.data_ptr(), flags.data_ptr(), _opt(pos), _opt(utf8), _opt(proto), n,
+                                _opt(stream_first), ns, _opt(carry_in), _opt(carry_out), _opt(msg_of),
+                                msgs.data_ptr(), cap, msg_count.data_ptr(), _opt(stream_msg_first), ws.ptr, ws.nbytes,
+                                _stream_handle(stream)), "kmws_msg_index")
 
 
 def unpack_unmask(wire, hdr_off, mode: int, out_desc, out_flags, out_err, ws: Workspace,
