@@ -1,29 +1,25 @@
 // The message table of a device batch for MI355X (gfx950): kmws_msg_index.  The
 // rule is stated in kmws_msg_rule.hpp; this file is the two segmented scans of
-// it over a batch of many streams' frames, modelled on kmws_proto.hip.
+// it over a batch of many streams' frames, both through the scan core of
+// kmws_stream_scan.hpp at four consecutive frames a lane.
 //
-// Scan A gives the state before each frame (is a message open, its head's b0,
-// has the stream had a data frame in this batch): two last-writer words in 11
-// bits under msg_compose, a stream's first frame composed behind the constant of
-// its carry.  Scan B needs that state: from it a frame's class follows (member,
-// starts a record, FIN), and a record's totals are a segmented sum (MsgSum: the
-// records started, and the running record's first and last member, member
-// count, FIN, bytes) that is reset where a record starts and at a stream's first
-// frame.  Five kernels, kMsgBlockFrames frames a block, four consecutive frames
-// a lane; a block scans its lanes' frames in registers, the wave by lane
-// shuffles, the four waves through four LDS entries:
+// Scan A (MsgStateOp) gives the state before each frame: two last-writer words
+// in 11 bits under msg_compose, a stream's first frame composed behind the
+// constant of its carry.  Scan B (MsgSumOp) needs that state: from it a frame's
+// class follows, and a record's totals are a segmented sum (MsgSum) that is
+// reset where a record starts and at a stream's first frame.  Five kernels:
 //   1. msg_state_kernel: a lane reads its frames' flags, finds the stream edges
 //      and scans the block's state functions; per block the aggregate.  Its lanes
 //      also check stream_first and the carries; status bits ride above the
 //      aggregate;
-//   2. msg_scan_states_kernel: one block scans those aggregates, a block of them
-//      a round, and stores the status word: cleared, or the OR of the blocks';
+//   2. msg_scan_states_kernel: scan_aggregates over those, and the status word's
+//      store: cleared, or the OR of the blocks';
 //   3. msg_class_kernel: scan A again, now behind the block's prefix: the state
 //      before every frame, its class, and with the members' lengths the block's
 //      scan B.  Per frame one 16-bit word (class, stream edges, the records
 //      started before it in the block), per block the aggregate;
-//   4. msg_scan_sums_kernel: one block scans those; *msg_count, and status bit 1
-//      when msg_cap is too small;
+//   4. msg_scan_sums_kernel: scan_aggregates over those; *msg_count, and status
+//      bit 1 when msg_cap is too small;
 //   5. msg_finish_kernel: scan B again from the stored words and the lengths,
 //      behind the block's prefix.  A record's totals are complete at the next
 //      reset point: the lane that owns it writes the record from the exclusive
@@ -38,87 +34,46 @@
 
 #include "kmws_common.hpp"
 #include "kmws_msg_rule.hpp"
-#include "kmws_utf8_dev.hpp"
+#include "kmws_stream_scan.hpp"
 #include "kmws_workspace.hpp"
 
 namespace kmws {
 
-constexpr int kMsgV = (int)kMsgFramesPerLane;
-constexpr int kMsgWaves = kBlock / 64;
-static_assert(kMsgBlockFrames == (uint32_t)kMsgV * kBlock && kMsgV == 4,
-              "a lane's frames are one 64-bit word of the per-frame array");
+constexpr int kMsgV = (int)kScanFramesPerLane;
+static_assert(kMsgV == 4, "a lane's frames are one 64-bit word of the per-frame array");
+static_assert(kMsgBlockFrames == kScanBlockFrames, "the constant the tests read");
 static_assert(sizeof(kmws_msg) == 48 && sizeof(kmws_msg_carry) == 16 && sizeof(MsgSum) == 24, "the ABI and the workspace");
 
 // The per-frame word: the class (bits 0-2), the frame is its stream's first /
 // last, and from bit 6 the records started before it in its block (< 1024).
 constexpr uint32_t kMsgClsFirst = 8u, kMsgClsLast = 16u;
 constexpr int kMsgClsStartsShift = 6;
-static_assert(((kMsgBlockFrames - 1) << kMsgClsStartsShift) <= 0xFFFFu, "the count fits the word");
+static_assert(((kScanBlockFrames - 1) << kMsgClsStartsShift) <= 0xFFFFu, "the count fits the word");
 
-// Exclusive scan over the block of one state function per lane; *total: the
-// whole block's.  s_wave: kMsgWaves words, free again after the next barrier.
-__device__ __forceinline__ uint32_t msg_block_scan(uint32_t f, uint32_t* s_wave, uint32_t* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const uint32_t up = __shfl_up(f, dlt);
-        if (lane >= dlt) f = msg_compose(up, f);
+struct MsgStateOp : ScanWordOp {  // scan A: one state function in 11 bits
+    static __device__ __forceinline__ T identity() { return msg_identity(); }
+    static __device__ __forceinline__ T compose(T a, T b) { return msg_compose(a, b); }
+};
+// Scan B.  A sum in memory is read and written field by field (a struct copy
+// through a pointer keeps it out of registers).
+struct MsgSumOp {
+    using T = MsgSum;
+    static __device__ __forceinline__ T identity() { return msg_sum_identity(); }
+    static __device__ __forceinline__ T compose(const T& a, const T& b) { return msg_sum_compose(a, b); }
+    static __device__ __forceinline__ T shfl_up(const T& v, int dlt)
+    {
+        T r;
+        r.starts = __shfl_up(v.starts, dlt), r.first = __shfl_up(v.first, dlt);
+        r.last = __shfl_up(v.last, dlt), r.frames = __shfl_up(v.frames, dlt);
+        r.bytes = __shfl_up((unsigned long long)v.bytes, dlt);
+        return r;
     }
-    const uint32_t before = __shfl_up(f, 1);
-    if (lane == 63) s_wave[wave] = f;
-    __syncthreads();
-    uint32_t pre = msg_identity(), tot = msg_identity();
-#pragma unroll
-    for (int w = 0; w < kMsgWaves; ++w) {
-        const uint32_t a = s_wave[w];
-        if (w < wave) pre = msg_compose(pre, a);
-        tot = msg_compose(tot, a);
+    static __device__ __forceinline__ T load(const T* p) { return T{p->starts, p->first, p->last, p->frames, p->bytes}; }
+    static __device__ __forceinline__ void store(T* p, const T& v)
+    {
+        p->starts = v.starts, p->first = v.first, p->last = v.last, p->frames = v.frames, p->bytes = v.bytes;
     }
-    *total = tot;
-    return lane ? msg_compose(pre, before) : pre;
-}
-
-__device__ __forceinline__ MsgSum msg_sum_shfl_up(const MsgSum& v, int dlt)
-{
-    MsgSum r;
-    r.starts = __shfl_up(v.starts, dlt), r.first = __shfl_up(v.first, dlt);
-    r.last = __shfl_up(v.last, dlt), r.frames = __shfl_up(v.frames, dlt);
-    r.bytes = __shfl_up((unsigned long long)v.bytes, dlt);
-    return r;
-}
-// A sum in memory, read and written field by field (a struct copy through a pointer keeps it out of registers).
-__device__ __forceinline__ MsgSum msg_sum_load(const MsgSum* p)
-{
-    return MsgSum{p->starts, p->first, p->last, p->frames, p->bytes};
-}
-__device__ __forceinline__ void msg_sum_store(MsgSum* p, const MsgSum& v)
-{
-    p->starts = v.starts, p->first = v.first, p->last = v.last, p->frames = v.frames, p->bytes = v.bytes;
-}
-// The same over one MsgSum per lane.
-__device__ __forceinline__ MsgSum msg_sum_block_scan(MsgSum f, MsgSum* s_wave, MsgSum* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const MsgSum up = msg_sum_shfl_up(f, dlt);
-        if (lane >= dlt) f = msg_sum_compose(up, f);
-    }
-    const MsgSum before = msg_sum_shfl_up(f, 1);
-    if (lane == 63) msg_sum_store(&s_wave[wave], f);
-    __syncthreads();
-    MsgSum pre = msg_sum_identity(), tot = msg_sum_identity();
-#pragma unroll
-    for (int w = 0; w < kMsgWaves; ++w) {
-        const MsgSum a = msg_sum_load(&s_wave[w]);
-        if (w < wave) pre = msg_sum_compose(pre, a);
-        tot = msg_sum_compose(tot, a);
-    }
-    *total = tot;
-    if (lane) pre = msg_sum_compose(pre, before);
-    return pre;
-}
+};
 
 // kmws_msg_carry has byte alignment: read and written byte by byte.
 __device__ __forceinline__ kmws_msg_carry msg_load_carry(const kmws_msg_carry* __restrict__ c, uint32_t s)
@@ -145,8 +100,7 @@ __device__ __forceinline__ void msg_lane_states(const uint16_t* __restrict__ fla
 #pragma unroll
     for (int k = 0; k < kMsgV; ++k) L.inc[k] = msg_identity(), L.b0[k] = 0x80u | KMWS_OP_PING, L.edge[k] = L.carried[k] = 0u;
     if (i0 >= n) return;
-    const uint32_t ilast = i0 + kMsgV - 1 < n ? i0 + kMsgV - 1 : n - 1;
-    const uint32_t s_lo = stream_of(first, ns, i0), s_hi = stream_of(first, ns, ilast);
+    const LaneStreams streams(first, ns, n, i0, kMsgV);
 #pragma unroll
     for (int k = 0; k < kMsgV; ++k) {
         const uint32_t i = i0 + k;
@@ -154,14 +108,14 @@ __device__ __forceinline__ void msg_lane_states(const uint16_t* __restrict__ fla
         if (i < n) {
             L.b0[k] = flags[i] & 0xFFu;
             f = msg_frame_fn(L.b0[k]);
-            const uint32_t s = s_lo == s_hi ? s_lo : stream_of(first, ns, i);
-            if (stream_begin(first, s) == i) {
-                const uint32_t c = carry_in ? carry_in[s].b[0] : 0u;
+            const FrameStream fs = streams.at(i);
+            if (fs.first) {
+                const uint32_t c = carry_in ? carry_in[fs.s].b[0] : 0u;
                 L.carried[k] = (c & kMsgOpen) ? c : 0u;
                 f = msg_compose(msg_const(L.carried[k]), f);
                 L.edge[k] |= kMsgClsFirst;
             }
-            if (i + 1u == stream_end(first, n, s)) L.edge[k] |= kMsgClsLast;
+            if (fs.last) L.edge[k] |= kMsgClsLast;
         }
         L.inc[k] = k ? msg_compose(L.inc[k - 1], f) : f;
     }
@@ -172,22 +126,19 @@ __global__ void __launch_bounds__(kBlock) msg_state_kernel(const uint16_t* __res
                                                            const kmws_msg_carry* __restrict__ carry_in,
                                                            uint32_t* __restrict__ aggs_a)
 {
-    __shared__ uint32_t s_wave[kMsgWaves];
+    __shared__ uint32_t s_wave[kScanWaves];
     const uint32_t i0 = (blockIdx.x * kBlock + threadIdx.x) * kMsgV;
     bool bad_args = false;
 #pragma unroll
     for (int k = 0; k < kMsgV; ++k) {
         const uint32_t x = i0 + k;
-        if (first && x <= ns) {  // stream_first: [0] == 0, ascending, [ns] == n
-            const uint32_t v = first[x];
-            bad_args |= (x == 0 && v != 0u) || (x == ns && v != n) || (x < ns && v > first[x + 1]);
-        }
+        bad_args |= stream_first_bad(first, ns, n, x);
         if (carry_in && x < ns) bad_args |= !msg_carry_ok(msg_load_carry(carry_in, x));
     }
     MsgLane L;
     msg_lane_states(flags, n, first, ns, carry_in, i0, L);
     uint32_t total;
-    msg_block_scan(L.inc[kMsgV - 1], s_wave, &total);
+    block_scan_excl<MsgStateOp>(L.inc[kMsgV - 1], s_wave, &total);
     const int any_bad = __syncthreads_or(bad_args ? 1 : 0);
     if (threadIdx.x == 0) aggs_a[blockIdx.x] = total | (any_bad ? kStatusBadDesc << 16 : 0u);
 }
@@ -198,25 +149,14 @@ __global__ void __launch_bounds__(kBlock) msg_scan_states_kernel(const uint32_t*
                                                                  uint32_t* __restrict__ pre_a, uint32_t nagg,
                                                                  WsHead* __restrict__ head)
 {
-    __shared__ uint32_t s_wave[kMsgWaves];
-    uint32_t run = msg_identity(), status = 0;
-    for (uint32_t c0 = 0; c0 < nagg; c0 += kMsgBlockFrames) {
-        const uint32_t b0 = c0 + threadIdx.x * kMsgV;
-        uint32_t inc[kMsgV];
-#pragma unroll
-        for (int k = 0; k < kMsgV; ++k) {
-            const uint32_t a = b0 + k < nagg ? aggs_a[b0 + k] : msg_identity();
-            status |= a >> 16;
-            inc[k] = k ? msg_compose(inc[k - 1], a & kMsgFnBits) : a & kMsgFnBits;
-        }
-        uint32_t total;
-        const uint32_t excl = msg_compose(run, msg_block_scan(inc[kMsgV - 1], s_wave, &total));
-#pragma unroll
-        for (int k = 0; k < kMsgV; ++k)
-            if (b0 + k < nagg) pre_a[b0 + k] = k ? msg_compose(excl, inc[k - 1]) : excl;
-        run = msg_compose(run, total);
-        __syncthreads();  // the next round rewrites s_wave
-    }
+    __shared__ uint32_t s_wave[kScanWaves];
+    uint32_t status = 0;
+    const auto load = [&](uint32_t b) {
+        const uint32_t a = b < nagg ? aggs_a[b] : msg_identity();
+        status |= a >> 16;
+        return a & kMsgFnBits;
+    };
+    scan_aggregates<MsgStateOp>(nagg, s_wave, load, [&](uint32_t b, uint32_t p) { pre_a[b] = p; });
     const int any_bad = __syncthreads_or((int)(status & kStatusBadDesc));
     if (threadIdx.x == 0) head->status = any_bad ? kStatusBadDesc : 0u;
 }
@@ -228,14 +168,14 @@ __global__ void __launch_bounds__(kBlock) msg_class_kernel(const kmws_desc* __re
                                                            const uint32_t* __restrict__ pre_a,
                                                            uint16_t* __restrict__ cls_out, MsgSum* __restrict__ aggs_b)
 {
-    __shared__ uint32_t s_wave[kMsgWaves];
-    __shared__ MsgSum s_sum[kMsgWaves];
+    __shared__ uint32_t s_wave[kScanWaves];
+    __shared__ MsgSum s_sum[kScanWaves];
     const uint32_t i0 = (blockIdx.x * kBlock + threadIdx.x) * kMsgV;
     MsgLane L;
     msg_lane_states(flags, n, first, ns, carry_in, i0, L);
     uint32_t total_a;
     // everything before the lane's first frame; a constant function unless that frame starts the batch
-    const uint32_t excl_a = msg_compose(pre_a[blockIdx.x], msg_block_scan(L.inc[kMsgV - 1], s_wave, &total_a));
+    const uint32_t excl_a = msg_compose(pre_a[blockIdx.x], block_scan_excl<MsgStateOp>(L.inc[kMsgV - 1], s_wave, &total_a));
 
     // Only the count of scan B is needed per frame here: the lane's frames are
     // folded into one sum for the block scan, the starts counted beside it.
@@ -256,13 +196,13 @@ __global__ void __launch_bounds__(kBlock) msg_class_kernel(const kmws_desc* __re
         }
     }
     MsgSum total;
-    const MsgSum excl = msg_sum_block_scan(lane_sum, s_sum, &total);
+    const MsgSum excl = block_scan_excl<MsgSumOp>(lane_sum, s_sum, &total);
     uint64_t word = 0;  // whole blocks in the workspace: no test against n
 #pragma unroll
     for (int k = 0; k < kMsgV; ++k)
         word |= (uint64_t)(cw[k] | ((msg_sum_starts(excl) + started[k]) << kMsgClsStartsShift)) << (16 * k);
     *reinterpret_cast<uint64_t*>(cls_out + i0) = word;
-    if (threadIdx.x == 0) msg_sum_store(&aggs_b[blockIdx.x], total);
+    if (threadIdx.x == 0) MsgSumOp::store(&aggs_b[blockIdx.x], total);
 }
 
 // pre_b[b] = the composition of aggs_b[0 .. b), pre_b[nblk] = the batch's total;
@@ -272,29 +212,16 @@ __global__ void __launch_bounds__(kBlock) msg_scan_sums_kernel(const MsgSum* __r
                                                                uint32_t msg_cap, uint32_t* __restrict__ msg_count,
                                                                WsHead* __restrict__ head)
 {
-    __shared__ MsgSum s_sum[kMsgWaves];
-    MsgSum run = msg_sum_identity();
-    for (uint32_t c0 = 0; c0 < nblk; c0 += kMsgBlockFrames) {
-        const uint32_t b0 = c0 + threadIdx.x * kMsgV;
-        MsgSum a[kMsgV], lane_sum = msg_sum_identity();
-#pragma unroll
-        for (int k = 0; k < kMsgV; ++k) {
-            a[k] = msg_sum_load(&aggs_b[b0 + k < nblk ? b0 + k : 0u]);  // nblk >= 1
-            if (b0 + k >= nblk) a[k] = msg_sum_identity();
-            lane_sum = msg_sum_compose(lane_sum, a[k]);
-        }
-        MsgSum total;
-        MsgSum before = msg_sum_compose(run, msg_sum_block_scan(lane_sum, s_sum, &total));
-#pragma unroll
-        for (int k = 0; k < kMsgV; ++k) {
-            if (b0 + k < nblk) msg_sum_store(&pre_b[b0 + k], before);
-            before = msg_sum_compose(before, a[k]);
-        }
-        run = msg_sum_compose(run, total);
-        __syncthreads();  // the next round rewrites s_sum
-    }
+    __shared__ MsgSum s_sum[kScanWaves];
+    const auto load = [&](uint32_t b) {
+        MsgSum a = MsgSumOp::load(&aggs_b[b < nblk ? b : 0u]);  // nblk >= 1
+        if (b >= nblk) a = msg_sum_identity();
+        return a;
+    };
+    const MsgSum run = scan_aggregates<MsgSumOp>(nblk, s_sum, load,
+                                                 [&](uint32_t b, const MsgSum& p) { MsgSumOp::store(&pre_b[b], p); });
     if (threadIdx.x == 0) {
-        msg_sum_store(&pre_b[nblk], run);
+        MsgSumOp::store(&pre_b[nblk], run);
         const uint32_t count = msg_sum_starts(run);
         *msg_count = count;
         if (count > msg_cap) head->status = head->status | kStatusBadDesc;
@@ -349,7 +276,7 @@ __global__ void __launch_bounds__(kBlock) msg_finish_kernel(MsgArrays a, uint32_
                                                             const uint16_t* __restrict__ cls,
                                                             const MsgSum* __restrict__ pre_b, uint32_t nblk)
 {
-    __shared__ MsgSum s_sum[kMsgWaves];
+    __shared__ MsgSum s_sum[kScanWaves];
     const uint32_t i0 = (blockIdx.x * kBlock + threadIdx.x) * kMsgV;
     if (blockIdx.x < nblk) {  // the same for the whole block: the barrier inside is met by all or none
         const uint64_t word = *reinterpret_cast<const uint64_t*>(cls + i0);
@@ -364,7 +291,7 @@ __global__ void __launch_bounds__(kBlock) msg_finish_kernel(MsgArrays a, uint32_
             lane_sum = msg_sum_compose(lane_sum, e[k]);
         }
         MsgSum total;
-        MsgSum in = msg_sum_compose(msg_sum_load(&pre_b[blockIdx.x]), msg_sum_block_scan(lane_sum, s_sum, &total));
+        MsgSum in = msg_sum_compose(MsgSumOp::load(&pre_b[blockIdx.x]), block_scan_excl<MsgSumOp>(lane_sum, s_sum, &total));
 #pragma unroll
         for (int k = 0; k < kMsgV; ++k) {
             const uint32_t i = i0 + k;
@@ -391,7 +318,7 @@ __global__ void __launch_bounds__(kBlock) msg_finish_kernel(MsgArrays a, uint32_
         if (s > a.ns) continue;
         const uint32_t f = s < a.ns ? stream_begin(a.first, s) : n;
         if (stream_msg_first)  // the records before the stream's first frame; past the last frame: all
-            stream_msg_first[s] = f < n ? msg_sum_starts(pre_b[f / kMsgBlockFrames]) + (cls[f] >> kMsgClsStartsShift)
+            stream_msg_first[s] = f < n ? msg_sum_starts(pre_b[f / kScanBlockFrames]) + (cls[f] >> kMsgClsStartsShift)
                                         : msg_sum_starts(pre_b[nblk]);
         if (carry_out && s < a.ns && f >= stream_end(a.first, n, s))  // an empty stream keeps its carry
             msg_store_carry(carry_out, s, msg_load_carry(a.carry_in, s));
@@ -426,8 +353,8 @@ kmws_status kmws_msg_index(const kmws_desc* descs, const uint16_t* flags, const 
 {
     if (!msg_count || !workspace) return KMWS_ERR_INVALID_PARAM;
     const MsgWs w = msg_ws(n, n_streams);
-    const kmws_status st = utf8_stream_args_check(descs && flags && msgs, nullptr, nullptr, n, stream_first, n_streams,
-                                                  n ? w.total : 0, workspace_bytes);
+    const kmws_status st = stream_args_check(descs && flags && msgs, nullptr, nullptr, n, stream_first, n_streams,
+                                             n ? w.total : 0, workspace_bytes);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) {
@@ -443,8 +370,7 @@ kmws_status kmws_msg_index(const kmws_desc* descs, const uint16_t* flags, const 
     MsgSum* aggs_b = at<MsgSum>(workspace, w.aggs_b);
     MsgSum* pre_b = at<MsgSum>(workspace, w.pre_b);
     uint16_t* cls = at<uint16_t>(workspace, w.cls);
-    // without stream_first there is one stream: its carry is checked by block 0
-    const uint32_t nagg = stream_first ? w.nagg : w.nblk;
+    const uint32_t nagg = w.first_pass(stream_first);
     hipLaunchKernelGGL(msg_state_kernel, dim3(nagg), dim3(kBlock), 0, s, flags, n, stream_first, n_streams, carry_in,
                        aggs_a);
     hipLaunchKernelGGL(msg_scan_states_kernel, dim3(1), dim3(kBlock), 0, s, aggs_a, pre_a, nagg, head);

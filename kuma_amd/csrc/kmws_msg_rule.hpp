@@ -38,9 +38,7 @@
 
 namespace kmws {
 
-// Frames one block of the device scans covers (kmws_msg.hip): 256 lanes, four
-// consecutive frames each.  The scans of the block aggregates take as many per round.
-constexpr uint32_t kMsgFramesPerLane = 4;
+// kScanBlockFrames (kmws_stream_scan.hpp; kmws_msg.hip ties them), exported for the tests, which read this line.
 constexpr uint32_t kMsgBlockFrames = 1024;
 
 // ---- scan A ----

@@ -47,6 +47,7 @@
 // the second axis) and the form, handed to copy_front.
 #include "kmws_common.hpp"
 #include "kmws_frame_parse.hpp"
+#include "kmws_stream_scan.hpp"
 #include "kmws_utf8_dev.hpp"
 #include "kmws_workspace.hpp"
 
@@ -2403,15 +2404,15 @@ static kmws_status launch_copy_tail(const uint8_t* src, uint8_t* dst, uint64_t c
 
 // The argument checks of the nine copy entries (args_ok: the entry's own).
 // Encode, gather and reframe: whatever fails, BUFFER_TOO_SMALL if a workspace is there and
-// too small, else INVALID_PARAM; the reframe then needs a device.  The validating forms: utf8_stream_args_check.
+// too small, else INVALID_PARAM; the reframe then needs a device.  The validating forms: stream_args_check.
 template <class Form>
 static kmws_status copy_args_check(bool args_ok, const void* src, const void* dst, uint32_t n, const CopyWs& c,
                                    size_t workspace_bytes, const Form& form)
 {
     if constexpr (Form::kUtf8) {
         if (!args_ok) return KMWS_ERR_INVALID_PARAM;
-        return utf8_stream_args_check(true, src, dst, n, form.stream_first, form.n_streams, c.w.total,
-                                      workspace_bytes);
+        return stream_args_check(true, src, dst, n, form.stream_first, form.n_streams, c.w.total,
+                                 workspace_bytes);
     } else {
         if (!args_ok || (reinterpret_cast<uintptr_t>(dst) & 15u) || (reinterpret_cast<uintptr_t>(src) & 15u) ||
             !c.ws || workspace_bytes < c.w.total)

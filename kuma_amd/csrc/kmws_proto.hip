@@ -5,21 +5,20 @@
 // What a frame does to its stream's state (IDLE / OPEN / CLOSED / FAILED) is a
 // function on four states packed in one byte, and a stream's first frame is
 // composed behind the constant function of the carried state, so the state
-// before every frame is a plain scan of bytes under proto_compose.  Three
-// kernels, kProtoBlockFrames frames a block, four consecutive frames a lane:
+// before every frame is a plain scan of bytes under proto_compose: the scan
+// core of kmws_stream_scan.hpp with ProtoOp, four consecutive frames a lane.
+// Three kernels:
 //   1. proto_elem_kernel: a lane reads its frames' descriptors, flags and error
 //      bytes, decides each frame's local class (a lane that owns a CLOSE frame
 //      walks its at most 125 payload bytes serially: the other 63 lanes of its
 //      wave wait, and CLOSE frames are at most one per connection), finds the
-//      stream edges, scans the block -- the lane's four frames in registers,
-//      the wave by lane shuffles on the packed byte, the four waves through
-//      four LDS words -- and stores per frame the local class (with the stream
-//      edge bits) and the block-inclusive function, per block the aggregate.
-//      Its lanes also check stream_first and the carries.  Status bits do not
-//      go to the status word (no kernel has cleared it yet) but ride above the
-//      block's aggregate;
-//   2. proto_scan_aggs_kernel: one block scans the aggregates, a block of them
-//      a round, and stores the status word: cleared, or the OR of the blocks';
+//      stream edges, scans the block and stores per frame the local class (with
+//      the stream edge bits) and the block-inclusive function, per block the
+//      aggregate.  Its lanes also check stream_first and the carries.  Status
+//      bits do not go to the status word (no kernel has cleared it yet) but ride
+//      above the block's aggregate;
+//   2. proto_scan_aggs_kernel: scan_aggregates, and the status word's store:
+//      cleared, or the OR of the blocks';
 //   3. proto_finish_kernel: element-wise.  The state before frame i is the
 //      block's prefix composed with the inclusive value of frame i - 1 applied
 //      to any state (a constant function since the stream's first frame), or the
@@ -29,43 +28,23 @@
 // read, 1 stored by kernel 3.  Vector stores and plain C++ only.
 #include "kmws_common.hpp"
 #include "kmws_proto_rule.hpp"
-#include "kmws_utf8_dev.hpp"
+#include "kmws_stream_scan.hpp"
 #include "kmws_workspace.hpp"
 
 namespace kmws {
 
-constexpr int kProtoV = (int)kProtoFramesPerLane;
-constexpr int kProtoWaves = kBlock / 64;
-static_assert(kProtoBlockFrames == (uint32_t)kProtoV * kBlock && kProtoV == 4,
-              "a lane's frames are one 32-bit word of the per-frame arrays");
+constexpr int kProtoV = (int)kScanFramesPerLane;
+static_assert(kProtoV == 4, "a lane's frames are one 32-bit word of the per-frame arrays");
+static_assert(kProtoBlockFrames == kScanBlockFrames, "the constant the tests read");
+
+struct ProtoOp : ScanWordOp {  // one state function in a byte
+    static __device__ __forceinline__ T identity() { return proto_identity(); }
+    static __device__ __forceinline__ T compose(T a, T b) { return proto_compose(a, b); }
+};
 
 // The per-frame byte beside the local class (bits 0-3): the frame is its
 // stream's first (its carried state in bits 4-5) / its stream's last.
 constexpr uint32_t kProtoFirst = 0x40u, kProtoLast = 0x80u;
-
-// Exclusive scan over the block of one function byte per lane; *total: the
-// whole block's.  s_wave: kProtoWaves words, free again after the next barrier.
-__device__ __forceinline__ uint32_t proto_block_scan(uint32_t f, uint32_t* s_wave, uint32_t* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const uint32_t up = __shfl_up(f, dlt);
-        if (lane >= dlt) f = proto_compose(up, f);
-    }
-    const uint32_t before = __shfl_up(f, 1);
-    if (lane == 63) s_wave[wave] = f;
-    __syncthreads();
-    uint32_t pre = proto_identity(), tot = proto_identity();
-#pragma unroll
-    for (int w = 0; w < kProtoWaves; ++w) {
-        const uint32_t a = s_wave[w];
-        if (w < wave) pre = proto_compose(pre, a);
-        tot = proto_compose(tot, a);
-    }
-    *total = tot;
-    return lane ? proto_compose(pre, before) : pre;
-}
 
 __device__ __forceinline__ uint32_t proto_load_carry(const kmws_proto_carry* __restrict__ c, uint32_t s)
 {
@@ -88,16 +67,13 @@ __global__ void __launch_bounds__(kBlock) proto_elem_kernel(const uint8_t* __res
                                                             uint8_t* __restrict__ incl_out,
                                                             uint16_t* __restrict__ aggs, uint32_t nblk)
 {
-    __shared__ uint32_t s_wave[kProtoWaves];
+    __shared__ uint32_t s_wave[kScanWaves];
     const uint32_t i0 = (blockIdx.x * kBlock + threadIdx.x) * kProtoV;
     bool bad_args = false;
 #pragma unroll
     for (int k = 0; k < kProtoV; ++k) {
         const uint32_t x = i0 + k;
-        if (first && x <= ns) {  // stream_first: [0] == 0, ascending, [ns] == n
-            const uint32_t v = first[x];
-            bad_args |= (x == 0 && v != 0u) || (x == ns && v != n) || (x < ns && v > first[x + 1]);
-        }
+        bad_args |= stream_first_bad(first, ns, n, x);
         if (x < ns) bad_args |= proto_load_carry(carry_in, x) > kProtoFailed;
     }
 
@@ -106,8 +82,7 @@ __global__ void __launch_bounds__(kBlock) proto_elem_kernel(const uint8_t* __res
 #pragma unroll
     for (int k = 0; k < kProtoV; ++k) inc[k] = proto_identity();
     if (i0 < n) {
-        const uint32_t ilast = i0 + kProtoV - 1 < n ? i0 + kProtoV - 1 : n - 1;
-        const uint32_t s_lo = stream_of(first, ns, i0), s_hi = stream_of(first, ns, ilast);
+        const LaneStreams streams(first, ns, n, i0, kProtoV);
 #pragma unroll
         for (int k = 0; k < kProtoV; ++k) {
             const uint32_t i = i0 + k;
@@ -122,13 +97,13 @@ __global__ void __launch_bounds__(kBlock) proto_elem_kernel(const uint8_t* __res
                     local = proto_close_body(base + df.off, df.len, masked ? df.key : 0u);
             }
             uint32_t f = proto_frame_fn(local, b0);
-            const uint32_t s = s_lo == s_hi ? s_lo : stream_of(first, ns, i);
-            if (stream_begin(first, s) == i) {
-                const uint32_t c = proto_load_carry(carry_in, s) & 3u;
+            const FrameStream fs = streams.at(i);
+            if (fs.first) {
+                const uint32_t c = proto_load_carry(carry_in, fs.s) & 3u;
                 f = proto_compose(proto_const(c), f);
                 local |= kProtoFirst | (c << 4);
             }
-            if (i + 1u == stream_end(first, n, s)) local |= kProtoLast;
+            if (fs.last) local |= kProtoLast;
             lw |= local << (8 * k);
             inc[k] = k ? proto_compose(inc[k - 1], f) : f;
         }
@@ -137,7 +112,7 @@ __global__ void __launch_bounds__(kBlock) proto_elem_kernel(const uint8_t* __res
             if (i0 + k >= n) inc[k] = inc[k - 1];
     }
     uint32_t total;
-    const uint32_t excl = proto_block_scan(inc[kProtoV - 1], s_wave, &total);
+    const uint32_t excl = block_scan_excl<ProtoOp>(inc[kProtoV - 1], s_wave, &total);
     if (blockIdx.x < nblk) {  // whole blocks in the workspace: no test against n
         uint32_t iw = 0;
 #pragma unroll
@@ -155,25 +130,14 @@ __global__ void __launch_bounds__(kBlock) proto_scan_aggs_kernel(const uint16_t*
                                                                  uint8_t* __restrict__ pre, uint32_t nagg,
                                                                  WsHead* __restrict__ head)
 {
-    __shared__ uint32_t s_wave[kProtoWaves];
-    uint32_t run = proto_identity(), status = 0;
-    for (uint32_t c0 = 0; c0 < nagg; c0 += kProtoBlockFrames) {
-        const uint32_t b0 = c0 + threadIdx.x * kProtoV;
-        uint32_t inc[kProtoV];
-#pragma unroll
-        for (int k = 0; k < kProtoV; ++k) {
-            const uint32_t a = b0 + k < nagg ? aggs[b0 + k] : proto_identity();
-            status |= a >> 8;
-            inc[k] = k ? proto_compose(inc[k - 1], a & 0xFFu) : a & 0xFFu;
-        }
-        uint32_t total;
-        const uint32_t excl = proto_compose(run, proto_block_scan(inc[kProtoV - 1], s_wave, &total));
-#pragma unroll
-        for (int k = 0; k < kProtoV; ++k)
-            if (b0 + k < nagg) pre[b0 + k] = (uint8_t)(k ? proto_compose(excl, inc[k - 1]) : excl);
-        run = proto_compose(run, total);
-        __syncthreads();  // the next round rewrites s_wave
-    }
+    __shared__ uint32_t s_wave[kScanWaves];
+    uint32_t status = 0;
+    const auto load = [&](uint32_t b) {
+        const uint32_t a = b < nagg ? aggs[b] : proto_identity();
+        status |= a >> 8;
+        return a & 0xFFu;
+    };
+    scan_aggregates<ProtoOp>(nagg, s_wave, load, [&](uint32_t b, uint32_t p) { pre[b] = (uint8_t)p; });
     const int any_bad = __syncthreads_or((int)(status & kStatusBadDesc));
     if (threadIdx.x == 0) head->status = any_bad ? kStatusBadDesc : 0u;
 }
@@ -246,8 +210,8 @@ kmws_status kmws_proto_check(const uint8_t* base, uint64_t span, const kmws_desc
 {
     if (rsv_allowed & ~0x70u) return KMWS_ERR_INVALID_PARAM;
     const ProtoWs w = proto_ws(n, n_streams);
-    const kmws_status st = utf8_stream_args_check(base && descs && flags && out && workspace, base, nullptr, n,
-                                                  stream_first, n_streams, n ? w.total : 0, workspace_bytes);
+    const kmws_status st = stream_args_check(base && descs && flags && out && workspace, base, nullptr, n,
+                                             stream_first, n_streams, n ? w.total : 0, workspace_bytes);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) {  // every stream's state passes through
@@ -262,12 +226,11 @@ kmws_status kmws_proto_check(const uint8_t* base, uint64_t span, const kmws_desc
     uint8_t* pre = at<uint8_t>(workspace, w.pre);
     uint8_t* local = at<uint8_t>(workspace, w.local);
     uint8_t* incl = at<uint8_t>(workspace, w.incl);
-    // without stream_first there is one stream: its carry is checked by block 0
-    const uint32_t nagg = stream_first ? w.nagg : w.nblk;
+    const uint32_t nagg = w.first_pass(stream_first);
     hipLaunchKernelGGL(proto_elem_kernel, dim3(nagg), dim3(kBlock), 0, s, base, span, descs, flags, err, n,
                        payload_masked != 0, rsv_allowed, stream_first, n_streams, carry_in, local, incl, aggs, w.nblk);
     hipLaunchKernelGGL(proto_scan_aggs_kernel, dim3(1), dim3(kBlock), 0, s, aggs, pre, nagg, at<WsHead>(workspace, 0));
-    const uint32_t sblk = (uint32_t)ceil_div(n_streams, kProtoBlockFrames);
+    const uint32_t sblk = (uint32_t)ceil_div(n_streams, kScanBlockFrames);
     hipLaunchKernelGGL(proto_finish_kernel, dim3(carry_out && sblk > w.nblk ? sblk : w.nblk), dim3(kBlock), 0, s, flags,
                        n, stream_first, n_streams, carry_in, carry_out, local, incl, pre, out);
     return hip_status(hipGetLastError());

@@ -46,12 +46,10 @@ namespace kmws {
 
 constexpr uint32_t kProtoIdle = 0, kProtoOpen = 1, kProtoClosed = 2, kProtoFailed = 3;
 
-// Frames one block of the device scan covers (kmws_proto.hip): 256 lanes, four
-// consecutive frames each.  The scan of the block aggregates takes as many per round.
-constexpr uint32_t kProtoFramesPerLane = 4;
+// kScanBlockFrames (kmws_stream_scan.hpp; kmws_proto.hip ties them), exported for the tests, which read this line.
 constexpr uint32_t kProtoBlockFrames = 1024;
 
-KMWS_HD uint32_t proto_identity() { return 0xE4u; }                    // 3, 2, 1, 0 -> themselves
+KMWS_HD uint32_t proto_identity() { return 0xE4u; }                   // 3, 2, 1, 0 -> themselves
 KMWS_HD uint32_t proto_const(uint32_t state) { return (state & 3u) * 0x55u; }
 KMWS_HD uint32_t proto_apply(uint32_t f, uint32_t state) { return (f >> (2u * (state & 3u))) & 3u; }
 // a, then b

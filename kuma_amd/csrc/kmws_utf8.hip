@@ -8,12 +8,13 @@
 // A batch is many frames of many streams; messages are fragmented, a code point
 // may straddle fragments, control frames interleave, and a message may begin in
 // one batch and end in the next.  Five kernels after the unmask plan
-// (launch_plan: descriptor checks and the tile -> frame records):
+// (launch_plan: descriptor checks and the tile -> frame records); the first
+// three are the scan core of kmws_stream_scan.hpp with Utf8Op, one frame a lane:
 //   1. utf8_elem_kernel: lane i turns frame i into a scan element (Utf8Elem,
 //      kmws_utf8_rule.hpp: what the frame does to its stream's message state,
 //      with its own last <= 3 payload bytes), folds the stream's carry into a
 //      stream's first frame, seeds first_bad[i], and reduces its block;
-//   2. utf8_scan_aggs_kernel: one block scans the block aggregates;
+//   2. utf8_scan_aggs_kernel: scan_aggregates over the block aggregates;
 //   3. utf8_ctx_kernel: lane i gets the state before frame i, stores how the
 //      frame sees itself (checked?, slot, look-back at its first byte), applies
 //      rule (b) -- a FIN frame that ends inside a code point, which an empty
@@ -37,6 +38,7 @@
 // kmws_unpack_reframe_utf8 around the reframe's, with skip_flag naming the
 // frames that pass leaves out (control frames to kernels 1 and 3).
 #include "kmws_common.hpp"
+#include "kmws_stream_scan.hpp"
 #include "kmws_unmask_tile.hpp"
 #include "kmws_utf8_dev.hpp"
 #include "kmws_utf8_rule.hpp"
@@ -50,22 +52,14 @@ constexpr uint32_t kStatusBadStreams = kStatusBadDesc;  // a malformed stream_fi
 static_assert(sizeof(Utf8Elem) == kWsUtf8ElemBytes && sizeof(Utf8View) == sizeof(Utf8Elem),
               "the layout's element size; the views replace the elements in place");
 
-// Inclusive scan of one element per lane over the block (Hillis-Steele in LDS);
-// s[] holds the inclusive values on return.
-__device__ __forceinline__ Utf8Elem block_scan(Utf8Elem e, Utf8Elem* s)
-{
-    const int tid = threadIdx.x;
-    s[tid] = e;
-    __syncthreads();
-#pragma unroll
-    for (int dlt = 1; dlt < kBlock; dlt <<= 1) {
-        const Utf8Elem t = tid >= dlt ? utf8_combine(s[tid - dlt], s[tid]) : s[tid];
-        __syncthreads();
-        s[tid] = t;
-        __syncthreads();
-    }
-    return s[tid];
-}
+struct Utf8Op {  // two dwords, moved one by one
+    using T = Utf8Elem;
+    static __device__ __forceinline__ T identity() { return utf8_identity(); }
+    static __device__ __forceinline__ T compose(T a, T b) { return utf8_combine(a, b); }
+    static __device__ __forceinline__ T shfl_up(T v, int dlt) { return T{__shfl_up(v.slot, dlt), __shfl_up(v.w, dlt)}; }
+    static __device__ __forceinline__ T load(const T* p) { return T{p->slot, p->w}; }
+    static __device__ __forceinline__ void store(T* p, T v) { p->slot = v.slot, p->w = v.w; }
+};
 
 // kmws_utf8_carry has byte alignment: read and written byte by byte.
 __device__ __forceinline__ uint64_t load_carry(const kmws_utf8_carry* __restrict__ c, uint32_t s)
@@ -90,13 +84,9 @@ __global__ void __launch_bounds__(kBlock) utf8_elem_kernel(const uint8_t* __rest
                                                            Utf8Elem* __restrict__ aggs, uint32_t nblk,
                                                            WsHead* __restrict__ head)
 {
-    __shared__ Utf8Elem s_scan[kBlock];
+    __shared__ Utf8Elem s_wave[kScanWaves];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (first && i <= ns) {  // stream_first: [0] == 0, ascending, [ns] == n
-        const uint32_t x = first[i];
-        if ((i == 0 && x != 0u) || (i == ns && x != n) || (i < ns && x > first[i + 1]))
-            atomicOr(&head->status, kStatusBadStreams);
-    }
+    if (stream_first_bad(first, ns, n, i)) atomicOr(&head->status, kStatusBadStreams);
     Utf8Elem e = utf8_identity();
     if (i < n) {
         const kmws_desc df = d[i];
@@ -129,25 +119,18 @@ __global__ void __launch_bounds__(kBlock) utf8_elem_kernel(const uint8_t* __rest
         elems[i] = e;
         first_bad[i] = fb;
     }
-    const Utf8Elem inc = block_scan(e, s_scan);
-    if (threadIdx.x == kBlock - 1 && blockIdx.x < nblk) aggs[blockIdx.x] = inc;
+    Utf8Elem total;
+    block_scan_excl<Utf8Op>(e, s_wave, &total);
+    if (threadIdx.x == 0 && blockIdx.x < nblk) aggs[blockIdx.x] = total;
 }
 
-// pre[b] = the combination of aggs[0 .. b): one block, kBlock aggregates a round.
+// pre[b] = the combination of aggs[0 .. b).
 __global__ void __launch_bounds__(kBlock) utf8_scan_aggs_kernel(const Utf8Elem* __restrict__ aggs,
                                                                 Utf8Elem* __restrict__ pre, uint32_t nblk)
 {
-    __shared__ Utf8Elem s_scan[kBlock];
-    Utf8Elem run = utf8_identity();
-    for (uint32_t c0 = 0; c0 < nblk; c0 += kBlock) {
-        const uint32_t b = c0 + threadIdx.x;
-        const Utf8Elem e = b < nblk ? aggs[b] : utf8_identity();
-        block_scan(e, s_scan);
-        const Utf8Elem ex = threadIdx.x ? s_scan[threadIdx.x - 1] : utf8_identity();
-        if (b < nblk) pre[b] = utf8_combine(run, ex);
-        run = utf8_combine(run, s_scan[kBlock - 1]);
-        __syncthreads();  // the next round rewrites s_scan
-    }
+    __shared__ Utf8Elem s_wave[kScanWaves];
+    scan_aggregates<Utf8Op>(nblk, s_wave, [&](uint32_t b) { return b < nblk ? aggs[b] : utf8_identity(); },
+                            [&](uint32_t b, Utf8Elem p) { pre[b] = p; });
 }
 
 // The state before and after every frame.  Overwrites elems[i] with frame i's
@@ -160,12 +143,13 @@ __global__ void __launch_bounds__(kBlock) utf8_ctx_kernel(const uint16_t* __rest
                                                           uint32_t* __restrict__ first_bad,
                                                           Utf8Elem* __restrict__ carry_tmp)
 {
-    __shared__ Utf8Elem s_scan[kBlock];
+    __shared__ Utf8Elem s_wave[kScanWaves];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     const Utf8Elem e = i < n ? elems[i] : utf8_identity();
-    block_scan(e, s_scan);
+    Utf8Elem total;
+    const Utf8Elem excl = block_scan_excl<Utf8Op>(e, s_wave, &total);
     if (i >= n) return;
-    Utf8Elem before = utf8_combine(pre[blockIdx.x], threadIdx.x ? s_scan[threadIdx.x - 1] : utf8_identity());
+    Utf8Elem before = utf8_combine(pre[blockIdx.x], excl);
     const Utf8Elem after = utf8_combine(before, e);
     const uint32_t s = stream_of(first, ns, i);
     if (stream_begin(first, s) == i) {  // the scan's element already holds the carry: unfold it for the view
@@ -704,8 +688,8 @@ kmws_status launch_unmask_pieces_utf8(uint8_t* base, const kmws_desc* descs, con
     return hip_status(hipGetLastError());
 }
 
-kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
-                                   uint32_t n_streams, size_t need, size_t have)
+kmws_status stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
+                              uint32_t n_streams, size_t need, size_t have)
 {
     if (n >= 0x80000000u || n_streams >= 0x80000000u) return KMWS_ERR_INVALID_PARAM;
     if (n && !ptrs_ok) return KMWS_ERR_INVALID_PARAM;
@@ -786,7 +770,7 @@ static kmws_status fused_check(const uint8_t* base, bool ptrs_ok, uint32_t n, co
 {
     if (!decode_schedule(schedule < 0 ? default_schedule(span, n) : (uint32_t)schedule, sc))
         return KMWS_ERR_INVALID_PARAM;
-    return utf8_stream_args_check(ptrs_ok, base, nullptr, n, stream_first, n_streams, n ? w.total : 0, workspace_bytes);
+    return stream_args_check(ptrs_ok, base, nullptr, n, stream_first, n_streams, n ? w.total : 0, workspace_bytes);
 }
 
 // Behind a launched plan (and the header parse, if any): the look-back
@@ -840,8 +824,8 @@ kmws_status kmws_utf8_validate(const uint8_t* base, uint64_t span, const kmws_de
                                void* workspace, size_t workspace_bytes, void* stream)
 {
     const Utf8Ws w = utf8_ws(span, n, n_streams);
-    kmws_status st = utf8_stream_args_check(base && descs && flags && out && workspace, base, nullptr, n, stream_first,
-                                            n_streams, n ? w.total : 0, workspace_bytes);
+    kmws_status st = stream_args_check(base && descs && flags && out && workspace, base, nullptr, n, stream_first,
+                                       n_streams, n ? w.total : 0, workspace_bytes);
     if (st != KMWS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) return launch_utf8_carry_copy(n_streams, carry_in, carry_out, s);  // every stream's state passes through

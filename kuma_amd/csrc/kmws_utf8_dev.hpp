@@ -62,28 +62,6 @@ __device__ __forceinline__ void report_bad(uint32_t* __restrict__ first_bad, uin
     if (__builtin_nontemporal_load(&first_bad[slot]) > frame + 1u) atomicMin(&first_bad[slot], frame + 1u);
 }
 
-// The stream of frame i: the last s in [0, ns) with first[s] <= i (empty streams
-// before it share its start and lose).  Every index stays in range whatever the
-// array holds.  first == nullptr: one stream.
-__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ first, uint32_t ns, uint32_t i)
-{
-    if (!first) return 0u;
-    uint32_t lo = 0, hi = ns - 1;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (first[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint32_t stream_begin(const uint32_t* __restrict__ first, uint32_t s)
-{
-    return first ? first[s] : 0u;
-}
-__device__ __forceinline__ uint32_t stream_end(const uint32_t* __restrict__ first, uint32_t n, uint32_t s)
-{
-    return first ? first[s + 1] : n;
-}
-
 // ---- the per-frame kernels around a payload pass of another file ----
 // `fa`: where the frame arrays lie in `workspace` (kmws_workspace.hpp), whose
 // WsHead holds the status word.  launch_utf8_frame_state runs utf8_elem_kernel, utf8_scan_aggs_kernel and
@@ -116,12 +94,5 @@ void launch_utf8_frame_finish(void* workspace, const FrameArraysWs& fa, uint32_t
 // carry_out = carry_in for every stream (an empty batch).
 kmws_status launch_utf8_carry_copy(uint32_t n_streams, const kmws_utf8_carry* carry_in, kmws_utf8_carry* carry_out,
                                    hipStream_t s);
-// The argument checks every UTF-8 entry makes on its streams and workspace, in
-// this order: n and n_streams below 2^31; ptrs_ok for a batch with frames; a
-// and b (either may be null) 16-byte aligned; one stream, or stream_first and at
-// least one (all KMWS_ERR_INVALID_PARAM); `have` workspace bytes against `need`
-// (KMWS_ERR_BUFFER_TOO_SMALL); a gfx950 device (KMWS_ERR_NOT_SUPPORTED).
-kmws_status utf8_stream_args_check(bool ptrs_ok, const void* a, const void* b, uint32_t n, const uint32_t* stream_first,
-                                   uint32_t n_streams, size_t need, size_t have);
 
 }  // namespace kmws

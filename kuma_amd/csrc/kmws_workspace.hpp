@@ -18,7 +18,7 @@
 #pragma once
 #include "kmws_common.hpp"
 #include "kmws_msg_rule.hpp"
-#include "kmws_proto_rule.hpp"
+#include "kmws_stream_scan.hpp"
 
 namespace kmws {
 
@@ -153,53 +153,55 @@ inline CopyFamilyWs reframe_ws(uint32_t n, uint64_t cap) { return copy_family_ws
 inline CopyFamilyWs gather_utf8_ws(uint32_t n, uint64_t cap, uint32_t ns) { return copy_family_ws(n, cap, false, true, ns); }
 inline CopyFamilyWs reframe_utf8_ws(uint32_t n, uint64_t cap, uint32_t ns) { return copy_family_ws(n, cap, true, true, ns); }
 
-// kmws_proto_check: head | uint16_t aggs[nagg] | uint8_t pre[nagg] | uint8_t local[nblk * F]
-// | uint8_t incl[nblk * F], F = kProtoBlockFrames.  nblk blocks hold frames; the
-// element pass also runs over the n_streams + 1 entries of stream_first, so nagg
-// = the blocks of the longer of the two, each with an aggregate (the block's
-// state function, its status bits above it) and a scanned prefix.  The frame
-// arrays cover whole blocks: a lane stores its four frames' bytes as one word.
-struct ProtoWs {
+// The blocks of a per-stream scan at four frames a lane (kmws_stream_scan.hpp): nblk
+// blocks of F = kScanBlockFrames hold frames; the first pass also runs over the
+// n_streams + 1 entries of stream_first, so nagg = the blocks of the longer of the
+// two, each with an aggregate (its status bits above it) and a scanned prefix.
+struct StreamBlocks {
     uint32_t nblk, nagg;
+    // The first pass's blocks: without stream_first there is one stream, whose carry block 0 checks.
+    uint32_t first_pass(const uint32_t* stream_first) const { return stream_first ? nagg : nblk; }
+};
+inline StreamBlocks stream_blocks(uint32_t n, uint32_t n_streams)
+{
+    const uint32_t nblk = (uint32_t)ceil_div(n, kScanBlockFrames);
+    const uint32_t sblk = (uint32_t)ceil_div((uint64_t)n_streams + 1, kScanBlockFrames);
+    return StreamBlocks{nblk, nblk > sblk ? nblk : sblk};
+}
+
+// kmws_proto_check: head | uint16_t aggs[nagg] | uint8_t pre[nagg] | uint8_t local[nblk * F]
+// | uint8_t incl[nblk * F].  The frame arrays cover whole blocks: a lane stores its
+// four frames' bytes as one word.
+struct ProtoWs : StreamBlocks {
     uint64_t aggs, pre, local, incl, total;
 };
 inline ProtoWs proto_ws(uint32_t n, uint32_t n_streams)
 {
-    ProtoWs w{};
-    w.nblk = (uint32_t)ceil_div(n, kProtoBlockFrames);
-    const uint32_t sblk = (uint32_t)ceil_div((uint64_t)n_streams + 1, kProtoBlockFrames);
-    w.nagg = w.nblk > sblk ? w.nblk : sblk;
+    ProtoWs w{stream_blocks(n, n_streams)};
     w.aggs = r16(sizeof(WsHead));
     w.pre = w.aggs + r16((uint64_t)w.nagg * 2);
     w.local = w.pre + r16((uint64_t)w.nagg);
-    w.incl = w.local + (uint64_t)w.nblk * kProtoBlockFrames;
-    w.total = w.incl + (uint64_t)w.nblk * kProtoBlockFrames;
+    w.incl = w.local + (uint64_t)w.nblk * kScanBlockFrames;
+    w.total = w.incl + (uint64_t)w.nblk * kScanBlockFrames;
     return w;
 }
 
 // kmws_msg_index: head | uint32_t aggs_a[nagg] | uint32_t pre_a[nagg] | MsgSum aggs_b[nblk]
-// | MsgSum pre_b[nblk + 1] | uint16_t cls[nblk * F], F = kMsgBlockFrames.  nblk blocks
-// hold frames; the first pass also runs over the n_streams + 1 entries of
-// stream_first, so nagg = the blocks of the longer of the two (scan A: a block's
-// state function, its status bits above it).  Scan B has an aggregate per block of
-// frames, and its prefixes end with the batch's total.  cls covers whole blocks: a
-// lane stores its four frames' words as one.
-struct MsgWs {
-    uint32_t nblk, nagg;
+// | MsgSum pre_b[nblk + 1] | uint16_t cls[nblk * F].  Scan A has nagg aggregates;
+// scan B has an aggregate per block of frames, and its prefixes end with the
+// batch's total.  cls covers whole blocks: a lane stores its four frames' words as one.
+struct MsgWs : StreamBlocks {
     uint64_t aggs_a, pre_a, aggs_b, pre_b, cls, total;
 };
 inline MsgWs msg_ws(uint32_t n, uint32_t n_streams)
 {
-    MsgWs w{};
-    w.nblk = (uint32_t)ceil_div(n, kMsgBlockFrames);
-    const uint32_t sblk = (uint32_t)ceil_div((uint64_t)n_streams + 1, kMsgBlockFrames);
-    w.nagg = w.nblk > sblk ? w.nblk : sblk;
+    MsgWs w{stream_blocks(n, n_streams)};
     w.aggs_a = r16(sizeof(WsHead));
     w.pre_a = w.aggs_a + r16((uint64_t)w.nagg * 4);
     w.aggs_b = w.pre_a + r16((uint64_t)w.nagg * 4);
     w.pre_b = w.aggs_b + r16((uint64_t)w.nblk * sizeof(MsgSum));
     w.cls = w.pre_b + r16(((uint64_t)w.nblk + 1) * sizeof(MsgSum));
-    w.total = w.cls + (uint64_t)w.nblk * kMsgBlockFrames * 2;
+    w.total = w.cls + (uint64_t)w.nblk * kScanBlockFrames * 2;
     return w;
 }
 

@@ -406,6 +406,127 @@ def test_streams_cut_into_two_calls_joined_by_the_carry():
         assert np.array_equal(carry2[done], carry[done]), c
 
 
+# ---------------------------------------------------------------- frame-scan shapes
+
+SCAN_B = 256  # frames one block of the frame-state scan covers (FrameArraysWs: nblk = ceil(n / 256)), one a lane
+SCAN_SHAPES = [1, 63, 64, 65, SCAN_B - 1, SCAN_B, SCAN_B + 1, 2 * SCAN_B + 1, SCAN_B * SCAN_B + 3]
+SCAN_LAYOUTS = ["one_stream", "stream_per_frame", "block_edge_streams", "empty_streams"]
+# carries (kmws_utf8_rule.hpp: flags, then the look-back, most recent byte first) and the reference's state for each
+SCAN_CARRIES = {"pending": bytes([3, 0x82, 0xE2, 0, 0, 0, 0, 0]),  # a checked message that stopped inside U+20AC
+                "bad": bytes([7, 0x61, 0, 0, 0, 0, 0, 0]),         # a checked message already reported BAD
+                "binary": bytes([1, 0, 0, 0, 0, 0, 0, 0])}        # an open message that is not checked
+
+
+def scan_carry_state(kind):
+    st = ref.StreamState()
+    if kind is not None:
+        st.open, st.checked, st.bad = True, kind != "binary", kind == "bad"
+        if kind == "pending":
+            st.pending = ref.first_bad(b"\xe2\x82")[1]
+    return st
+
+
+def scan_stream_first(layout, n):
+    if layout == "one_stream":
+        return [0, n]
+    if layout == "stream_per_frame":
+        return list(range(n + 1))
+    if layout == "block_edge_streams":  # every wave edge, so every block edge: a stream ends on a block's last lane
+        return sorted({0, n} | set(range(64, n, 64)))
+    a, b = n // 3, 2 * n // 3           # empty streams first, in the middle and last
+    return [0, 0, 0, a, a, a, b, n, n, n]
+
+
+def scan_carry_after(frames, verdicts, carry):
+    """The carry a stream leaves (kmws_utf8_rule.hpp: utf8_carry_pack), from its
+    frames, the reference's verdicts on them and the carry it came with."""
+    is_open, checked, bad = bool(carry[0] & 1), bool(carry[0] & 2), bool(carry[0] & 4)
+    tail = bytes([carry[3], carry[2], carry[1]])
+    for (b0, p), v in zip(frames, verdicts):
+        if (b0 & 0x0F) >= 8:
+            continue
+        if b0 & 0x0F:
+            is_open, checked, bad, tail = True, (b0 & 0x0F) == 1 and not (b0 & RSV1), False, bytes(3)
+        if is_open:
+            tail = (tail + p)[-3:]
+            bad |= v in (ref.BAD, ref.AFTER_BAD)
+        if b0 & FIN:
+            is_open = False
+    if not is_open:
+        return bytes(8)
+    if not checked:
+        return bytes([1, 0, 0, 0, 0, 0, 0, 0])
+    return bytes([3 | (4 if bad else 0), tail[2], tail[1], tail[0], 0, 0, 0, 0])
+
+
+@functools.lru_cache(maxsize=None)
+def scan_case(layout, n):
+    """-> (batch, stream_first, carry_in, expected verdicts, expected carry_out)."""
+    first = scan_stream_first(layout, n)
+    ns = len(first) - 1
+    rng = random.Random(1000 * SCAN_LAYOUTS.index(layout) + n % 997)
+    lens = [rng.randint(0, 3) for _ in range(n)]
+    lens[0] = 1
+    frames = fill_messages(lens, 50 + n % 997, streams=first)
+    # the first stream's carry, also where that stream is empty; then every fifth stream a BAD or a binary carry
+    owner0 = max(s for s in range(ns) if first[s] == 0)
+    kinds = {s: ("bad" if s % 5 == 2 else "binary") for s in range(ns) if s % 5 in (2, 4) and first[s] < first[s + 1]}
+    kinds.update({0: "pending", owner0: "pending"})
+    frames[0] = (C_, b"\xac")  # completes the carried code point; the frames behind it continue that message
+    for s, kind in kinds.items():
+        if s != owner0 and first[s] < first[s + 1]:
+            b0, p = frames[first[s]]
+            frames[first[s]] = (C_ | (b0 & FIN), p)  # a CONTINUE of the carried message
+    # the first stream of four frames or more ends in a message that is BAD, goes on and stays open
+    long = [s for s in range(ns) if first[s + 1] - first[s] >= 4]
+    if long:
+        e = first[long[0] + 1]
+        frames[e - 3:e] = [(T_, b"\xff"), (C_, b"a"), (C_, b"b")]
+    carry_in = np.zeros((ns, 8), dtype=np.uint8)
+    for s, kind in kinds.items():
+        carry_in[s] = np.frombuffer(SCAN_CARRIES[kind], dtype=np.uint8)
+    expect, carry_out = [], np.zeros((ns, 8), dtype=np.uint8)
+    for s in range(ns):
+        st_frames = frames[first[s]:first[s + 1]]
+        res = ref.validate_stream(st_frames, scan_carry_state(kinds.get(s)))[0]
+        expect += res
+        carry_out[s] = np.frombuffer(scan_carry_after(st_frames, res, bytes(carry_in[s])), dtype=np.uint8)
+    offs, total = packed_offsets([len(p) for _, p in frames], rng)
+    return Batch(frames, offs, total, seed=n), first, carry_in, np.array(expect, dtype=np.uint8), carry_out
+
+
+def test_scan_shapes_are_informative():
+    """CPU, on the reference's verdicts: every case of 64 frames or more holds
+    all four verdicts, the carried code point is completed by frame 0, and the
+    streams leave every kind of carry."""
+    left = set()
+    for layout in SCAN_LAYOUTS:
+        for n in SCAN_SHAPES:
+            _, first, carry_in, expect, carry_out = scan_case(layout, n)
+            assert len(expect) == n and expect[0] == ref.OK and carry_in[0].any(), (layout, n)
+            assert n < 64 or {ref.OK, ref.BAD, ref.AFTER_BAD, ref.NOT_TEXT} <= set(expect), (layout, n, set(expect))
+            left |= set(carry_out[:, 0])
+    assert left == {0, 1, 3, 7}  # between messages, open unchecked, open checked, open checked and BAD
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SCAN_SHAPES)
+@pytest.mark.parametrize("layout", SCAN_LAYOUTS)
+def test_frame_scan_shapes(layout, n):
+    """The frame-state scan over wave edges, block edges and the second round of
+    the aggregate scan: 0-3 byte payloads, so code points straddle fragments and
+    the state matters across every edge."""
+    b, first, carry_in, expect, carry_want = scan_case(layout, n)
+    assert n < 64 or {ref.OK, ref.BAD, ref.AFTER_BAD, ref.NOT_TEXT} <= set(expect)
+    one = layout == "one_stream"
+    out, carry, st = run_gpu(b, masked=True, stream_first=None if one else first, carry_in=carry_in)
+    assert st == 0
+    bad = np.nonzero(out != expect)[0]
+    assert bad.size == 0, (bad[:10], out[bad[:10]], expect[bad[:10]])
+    bad = np.nonzero((carry != carry_want).any(axis=1))[0]
+    assert bad.size == 0, (bad[:10], carry[bad[:10]], carry_want[bad[:10]])
+
+
 # ---------------------------------------------------------------- contract
 
 @pytest.mark.gpu
