@@ -28,6 +28,12 @@ TEST_DEFINES = ("KMWS_TEST_SKIP_PUBLISH_TILE=1", "KMWS_LOOKBACK_SPIN_LIMIT=4096"
                 "KMWS_TEST_RESIDENT_STALL_KEY=0xDEAD5E00u", "KMWS_RESIDENT_TIMEOUT_MS=50",
                 "KMWS_RESIDENT_DRAIN_MS=150")
 RESIDENT_STALL_KEY = 0xDEAD5E00
+# Test-only probes of the scan core (csrc/kmws_stream_scan.hpp) under Ops that
+# show every scan mistake; tests/test_gpu_scan_core.py loads the library by path.
+# The source lies outside csrc/, so the product library's glob never sees it, and
+# inside the package, so this function needs nothing of tests/.
+SCAN_PROBE_SRC = os.path.join(HERE, "probes", "scan_probe.hip")
+SCAN_PROBE_LIB = os.path.join(LIB_DIR, "libkmws_scan_probe.so")
 
 
 def sources(srcdir: str | None = None):
@@ -85,7 +91,15 @@ def build_test_variants(force: bool = False) -> list:
     if force or not os.path.exists(TEST_LIB) or os.path.getmtime(TEST_LIB) < max(
             os.path.getmtime(p) for p in deps()):
         build(out=TEST_LIB, defines=TEST_DEFINES)
-    return [TEST_LIB]
+    probe_deps = [SCAN_PROBE_SRC] + glob.glob(os.path.join(HERE, "csrc", "*.hpp")) + \
+        glob.glob(os.path.join(ROOT, "include", "*.h"))
+    if force or not os.path.exists(SCAN_PROBE_LIB) or os.path.getmtime(SCAN_PROBE_LIB) < max(
+            os.path.getmtime(p) for p in probe_deps):
+        os.makedirs(LIB_DIR, exist_ok=True)
+        subprocess.check_call(["hipcc", "-x", "hip", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
+                               "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"),
+                               "-I", os.path.join(HERE, "csrc"), SCAN_PROBE_SRC, "-o", SCAN_PROBE_LIB])
+    return [TEST_LIB, SCAN_PROBE_LIB]
 
 
 if __name__ == "__main__":

@@ -251,6 +251,20 @@ def test_streams_cut_into_two_calls_joined_by_the_carry():
             assert np.array_equal(out1, expect[:c]), (c, form)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("second", [vt.OK_PIECE, vt.BAD_PIECE], ids=["ok", "bad"])
+def test_message_open_across_rounds(second):
+    """tests/test_gpu_utf8.py's round-two case through the fused gather: the frame
+    state crosses the first round of the aggregate scan (run_gather checks the
+    dense payload and the offsets as ever)."""
+    frames, at = vt.round_edge_frames(*vt.EDGE_ROUNDS[2], second)
+    expect = vt.round_edge_expect(frames, at, second)
+    out, carry = run_gather(vt.round_edge_batch(frames), "chunk")
+    bad = np.nonzero(out != expect)[0]
+    assert bad.size == 0, (bad[:10], out[bad[:10]], expect[bad[:10]])
+    assert bytes(carry[0]) == vt.scan_carry_after(frames, expect, bytes(8))
+
+
 # ---------------------------------------------------------------- 6. unpack form
 
 def run_unpack(wire, hdr, form, fused):

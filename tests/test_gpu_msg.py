@@ -109,6 +109,105 @@ def test_more_streams_than_frames():
     assert got["count"] == 2 and got["carries"][ns - 4] == mixed_carries(ns)[ns - 4]
 
 
+# ---------------------------------------------------------------- past one round of the aggregate scans
+
+# A round of an aggregate scan takes F aggregates of F frames, four a lane.  F * F + 3 (above) puts one
+# aggregate into round two: lane 0's first.  These put one into lane 1 of round two (1,029 aggregates), into
+# lane 64, past a wave edge (1,281), and into round three.
+ROUND_TWO_LANE_1 = F * F + 4 * F + 1
+ROUND_SHAPES = [ROUND_TWO_LANE_1, (F + 256) * F + 1, 2 * F * F + 1]
+
+
+@pytest.mark.parametrize("n", ROUND_SHAPES)
+def test_scan_rounds_one_stream(n):
+    assert -(-n // F) == {0: F + 5, 1: F + 257, 2: 2 * F + 1}[ROUND_SHAPES.index(n)]
+    mu.check([pattern(n)], one_stream=True, carries=[mr.carry(0x02, 9)])
+
+
+def test_scan_rounds_streams_end_at_block_boundaries():
+    n = ROUND_TWO_LANE_1
+    bounds = list(range(0, n, F)) + [n]
+    mu.check(cut(pattern(n), bounds), carries=mixed_carries(len(bounds) - 1))
+
+
+# the member's and the FIN's aggregates in round two: in lane 0, in lane 1, in lane 64 (past a wave edge)
+@pytest.mark.parametrize("mid_block", [F + 1, F + 5, F + 257])
+def test_message_open_across_rounds(mid_block):
+    """Head in block F - 2, a member with payload in mid_block, FIN in the block
+    after it, only PINGs between: the state of scan A and the 24-byte sum of scan
+    B cross the round edge through the aggregate scans' running prefix."""
+    n = (mid_block + 1) * F + 9
+    head, mid, fin = (F - 2) * F + 10, mid_block * F + 5, (mid_block + 1) * F + 7
+    frames = [pr.fr(pr.PING, payload=b"p")] * n
+    frames[head] = pr.fr(pr.B, 0, payload=b"head")
+    frames[mid] = pr.fr(pr.C, 0, payload=b"mid")
+    frames[fin] = pr.fr(pr.C, 1, payload=b"tail!")
+    got, _ = mu.check([frames], one_stream=True)
+    r = got["recs"]
+    assert got["count"] == 1 and (r["first"][0], r["last"][0], r["frames"][0], r["bytes"][0]) == (head, fin, 3, 12)
+    assert r["bits"][0] == mr.BEGIN | mr.END  # the PINGs' payloads lie between
+    frames[fin] = pr.fr(pr.PING)
+    frames[fin + 1] = pr.fr(pr.C, 0, payload=b"x")  # the batch's last frame a member, the message left open
+    got, _ = mu.check([frames], one_stream=True)
+    assert got["carries"] == [mr.carry(0x02, 8)]
+
+
+# ---------------------------------------------------------------- status bits and streams past round one
+
+def empty_streams_batch(ns):
+    """ns streams, all empty but the last two, and three frames: the first pass
+    runs over stream_first alone and has ceil((ns + 1) / F) aggregates."""
+    bounds = [0] * (ns - 2) + [0, 1, 3]
+    return cut([pr.fr(pr.C, 1, payload=b"abc"), pr.fr(pr.T, 0, payload=b"de"), pr.fr(pr.PING)], bounds), bounds
+
+
+NO_CARRY = b"\x7f" + bytes(15)  # test_malformed_carry_sets_status_bit_1
+
+
+def empty_streams_carries(ns):
+    """mixed_carries, and the first frame's stream comes with an open message: that CONTINUE|FIN ends it."""
+    c = mixed_carries(ns)
+    c[ns - 2] = mr.carry(0x01, 5)
+    return c
+
+
+def test_streams_past_one_round_without_frames():
+    """Follows test_more_streams_than_frames: the status bits ride above the
+    aggregates of round two; every empty stream's carry is copied and
+    stream_msg_first holds (mu.check compares both)."""
+    ns = F * F + 4 * F + 2
+    assert -(-(ns + 1) // F) == F + 5
+    streams, bounds = empty_streams_batch(ns)
+    carries = empty_streams_carries(ns)
+    got, _ = mu.check(streams, carries=carries)
+    assert got["count"] == 2 and got["carries"][:ns - 2] == carries[:ns - 2]
+    assert list(got["first_of"][[0, F * F, ns - 2, ns - 1, ns]]) == [0, 0, 0, 1, 2]
+    # round two's lane 1; round one's last lane
+    for x in (F * F + 4 * F + 1, F * F - 1):
+        first = list(bounds)
+        first[x] = first[x + 1] + 1  # descending
+        assert mu.run_gpu(streams, carries=carries, stream_first=first)["status"] == 1, x
+    for s in (F * F + 4 * F, F * F - 1):
+        c = list(carries)
+        c[s] = NO_CARRY
+        assert mu.run_gpu(streams, carries=c)["status"] == 1, s
+
+
+def test_streams_in_round_three_without_frames():
+    ns = 2 * F * F + 5
+    assert -(-(ns + 1) // F) == 2 * F + 1
+    streams, bounds = empty_streams_batch(ns)
+    carries = empty_streams_carries(ns)
+    got = mu.run_gpu(streams, carries=carries)
+    assert got["status"] == 0 and got["count"] == 2 and got["carries"][:ns - 2] == carries[:ns - 2]
+    first = list(bounds)
+    first[ns - 1] = first[ns] + 1  # the last aggregate
+    assert mu.run_gpu(streams, carries=carries, stream_first=first)["status"] == 1
+    c = list(carries)
+    c[ns - 1] = NO_CARRY
+    assert mu.run_gpu(streams, carries=c)["status"] == 1
+
+
 # ---------------------------------------------------------------- across blocks
 
 def test_message_open_across_blocks():

@@ -125,6 +125,102 @@ def test_more_streams_than_frames():
     check(cut([pr.fr(pr.C, 1), pr.fr(pr.T), pr.fr(pr.PING)], bounds), carry_in=carry)
 
 
+# ---------------------------------------------------------------- past one round of the aggregate scan
+
+# A round of the aggregate scan takes F aggregates of F frames, four a lane.  F * F + 3 (above) puts one
+# aggregate into round two: lane 0's first.  These put one into lane 1 of round two (1,029 aggregates), into
+# lane 64, past a wave edge (1,281), and into round three.
+ROUND_TWO_LANE_1 = F * F + 4 * F + 1
+ROUND_SHAPES = [ROUND_TWO_LANE_1, (F + 256) * F + 1, 2 * F * F + 1]
+
+
+@pytest.mark.parametrize("n", ROUND_SHAPES)
+def test_scan_rounds_one_stream(n):
+    """The stream comes with an open message, which frame 0 ends."""
+    assert -(-n // F) == {0: F + 5, 1: F + 257, 2: 2 * F + 1}[ROUND_SHAPES.index(n)]
+    frames = [pr.fr(pr.C, 1)] + pattern(n - 1, True)
+    out = check([frames], one_stream=True, carry_in=[pr.OPEN])
+    assert out[0] == pr.OK and not out[:(n - 1) * 9 // 10].any()
+
+
+def test_scan_rounds_streams_end_at_block_boundaries():
+    n = ROUND_TWO_LANE_1
+    frames = pattern(n, False)
+    check(cut(frames, list(range(0, n, F)) + [n]))
+
+
+# the stray frame's aggregate in round two: lane 0's second, lane 1's second, lane 64's second (past a wave edge)
+@pytest.mark.parametrize("stray_block", [F + 1, F + 5, F + 257])
+def test_message_open_across_rounds(stray_block):
+    """A message opened in block F - 2 is still open in the stray head's block,
+    past the round edge: that head is a sequence error only because the state
+    arrived through the aggregate scan's running prefix.  FAILED then reaches the
+    last block.  The same with a CLOSE before the edge and data behind it."""
+    n = (stray_block + 2) * F + 8
+    head, stray = (F - 2) * F + 10, stray_block * F + 5
+    frames = [pr.fr(pr.PING)] * n
+    frames[head] = pr.fr(pr.T, 0)
+    frames[stray] = pr.fr(pr.T, 0)
+    out = check([frames], one_stream=True)
+    assert not out[:stray].any() and out[stray] == pr.INTERLEAVED and (out[stray + 1:] == pr.AFTER_FAIL).all()
+    assert pu.expect([frames])[1][0] == pr.FAILED
+    frames[head] = pr.close(1000, b"bye")
+    frames[stray] = pr.fr(pr.T)
+    out = check([frames], one_stream=True)
+    assert not out[:head + 1].any() and (out[head + 1:] == pr.AFTER_CLOSE).all()
+    assert pu.expect([frames])[1][0] == pr.CLOSED
+
+
+# ---------------------------------------------------------------- status bits and streams past round one
+
+def empty_streams_batch(ns):
+    """ns streams, all empty but the last two, and three frames: the first pass
+    runs over stream_first alone and has ceil((ns + 1) / F) aggregates."""
+    bounds = [0] * (ns - 2) + [0, 1, 3]
+    return cut([pr.fr(pr.C, 1), pr.fr(pr.T), pr.fr(pr.PING)], bounds), bounds
+
+
+def test_streams_past_one_round_without_frames():
+    """Follows test_more_streams_than_frames: the status bits ride above the
+    aggregates of round two, and every empty stream's carry is copied."""
+    ns = F * F + 4 * F + 2
+    assert -(-(ns + 1) // F) == F + 5
+    streams, bounds = empty_streams_batch(ns)
+    carry = np.array([k & 3 for k in range(ns)], dtype=np.uint8)
+    check(streams, carry_in=carry)
+    b = pr.device_batch(streams)
+    # (index, in words): round two's lane 1; round one's last lane
+    for x in (F * F + 4 * F + 1, F * F - 1):
+        first = list(bounds)
+        first[x] = first[x + 1] + 1  # descending
+        b["stream_first"] = first
+        assert pu.run_gpu(b, carry_in=carry)[2] == 1, x
+    b["stream_first"] = bounds
+    for s in (F * F + 4 * F, F * F - 1):
+        c = carry.copy()
+        c[s] = 7  # no state
+        assert pu.run_gpu(b, carry_in=c)[2] == 1, s
+    assert pu.run_gpu(b, carry_in=carry)[2] == 0
+
+
+def test_streams_in_round_three_without_frames():
+    ns = 2 * F * F + 5
+    assert -(-(ns + 1) // F) == 2 * F + 1
+    streams, bounds = empty_streams_batch(ns)
+    carry = np.array([k & 3 for k in range(ns)], dtype=np.uint8)
+    b = pr.device_batch(streams)
+    out, states, st = pu.run_gpu(b, carry_in=carry)
+    assert st == 0 and np.array_equal(states[:ns - 2], carry[:ns - 2])  # the empty streams' carries, copied
+    first = list(bounds)
+    first[ns - 1] = first[ns] + 1  # the last aggregate
+    b["stream_first"] = first
+    assert pu.run_gpu(b, carry_in=carry)[2] == 1
+    b["stream_first"] = bounds
+    c = carry.copy()
+    c[ns - 1] = 7
+    assert pu.run_gpu(b, carry_in=c)[2] == 1
+
+
 # ---------------------------------------------------------------- across blocks
 
 def test_message_open_across_blocks():

@@ -238,6 +238,17 @@ def test_streams_cut_into_two_calls_joined_by_the_carry():
     assert after_bad_through_carry >= 1
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("second", [vt.OK_PIECE, vt.BAD_PIECE], ids=["ok", "bad"])
+def test_message_open_across_rounds(second):
+    """tests/test_gpu_utf8.py's round-two case through the fused entry: the frame
+    state crosses the first round of the aggregate scan; the arena comes out plain."""
+    frames, at = vt.round_edge_frames(*vt.EDGE_ROUNDS[2], second)
+    expect = vt.round_edge_expect(frames, at, second)
+    _, carry = u.check_fused(u.nonzero_keys(vt.round_edge_batch(frames)), expect)
+    assert bytes(carry[0]) == vt.scan_carry_after(frames, expect, bytes(8))
+
+
 # ---------------------------------------------------------------- 7. composition parity
 
 FUZZ_SEEDS = range(40)

@@ -4,7 +4,9 @@ boundary, code points straddling fragments, the unmask tests' frame layouts
 masked and plain, streams with the carry between two calls, the contract, and a
 seeded fuzz whose mix is checked on the reference's verdicts."""
 import functools
+import os
 import random
+import re
 
 import numpy as np
 import pytest
@@ -12,6 +14,7 @@ import pytest
 import utf8_ref as ref
 
 T_, C_, B_, FIN, RSV1, PING = 1, 0, 2, 0x80, 0x40, 9
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---------------------------------------------------------------- helpers
@@ -32,12 +35,32 @@ class Batch:
         self.flags = np.array([b0 for b0, _ in self.frames], dtype=np.int64) | 0x100
         self.plain = rng.integers(0x80, 0x100, size=(self.total + 15) // 16 * 16, dtype=np.uint8)
         assert self.n == 0 or (self.offs[-1] + self.lens[-1] <= self.total)
-        for (_, p), o in zip(self.frames, self.offs):
-            if p:
-                self.plain[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+        if self.disjoint():
+            at, _ = self.payload_index()
+            self.plain[at] = np.frombuffer(b"".join(p for _, p in self.frames), dtype=np.uint8)
+        else:
+            for (_, p), o in zip(self.frames, self.offs):
+                if p:
+                    self.plain[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+
+    def disjoint(self):
+        """Few payload bytes, in ascending order without overlap (a test may move
+        offs afterwards): one indexed pass serves.  Else frame by frame."""
+        return int(self.lens.sum()) <= 1 << 22 and bool((self.offs[1:] >= self.offs[:-1] + self.lens[:-1]).all())
+
+    def payload_index(self):
+        """Per payload byte, frame after frame: its arena index and its position in its frame."""
+        start = np.cumsum(self.lens) - self.lens
+        within = np.arange(int(self.lens.sum()), dtype=np.int64) - np.repeat(start, self.lens)
+        return np.repeat(self.offs, self.lens) + within, within
 
     def masked(self):
         buf = self.plain.copy()
+        if self.disjoint():  # one pass over all payload bytes: a key's byte j & 3 on a frame's byte j
+            at, within = self.payload_index()
+            shift = ((within & 3) * 8).astype(np.uint32)
+            buf[at] ^= ((np.repeat(self.keys, self.lens) >> shift) & np.uint32(0xFF)).astype(np.uint8)
+            return buf
         for o, L, k in zip(self.offs, self.lens, self.keys):
             if L:
                 kb = np.frombuffer(np.uint32(k).tobytes(), dtype=np.uint8)
@@ -408,7 +431,16 @@ def test_streams_cut_into_two_calls_joined_by_the_carry():
 
 # ---------------------------------------------------------------- frame-scan shapes
 
-SCAN_B = 256  # frames one block of the frame-state scan covers (FrameArraysWs: nblk = ceil(n / 256)), one a lane
+def header_constant(header, name):
+    """A constexpr integer of kuma_amd/csrc/<header>."""
+    txt = open(os.path.join(ROOT, "kuma_amd", "csrc", header)).read()
+    return int(re.search(r"constexpr \w+ %s = (\d+);" % name, txt).group(1))
+
+
+# frames one block of the frame-state scan covers (FrameArraysWs: nblk = ceil(n / kBlock)), one a lane
+SCAN_B = header_constant("kmws_common.hpp", "kBlock")
+SCAN_R = header_constant("kmws_stream_scan.hpp", "kScanBlockFrames")  # aggregates one round of scan_aggregates takes
+SCAN_U = SCAN_B * SCAN_R  # frames whose aggregates fill one round
 SCAN_SHAPES = [1, 63, 64, 65, SCAN_B - 1, SCAN_B, SCAN_B + 1, 2 * SCAN_B + 1, SCAN_B * SCAN_B + 3]
 SCAN_LAYOUTS = ["one_stream", "stream_per_frame", "block_edge_streams", "empty_streams"]
 # carries (kmws_utf8_rule.hpp: flags, then the look-back, most recent byte first) and the reference's state for each
@@ -513,11 +545,16 @@ def test_scan_shapes_are_informative():
 @pytest.mark.parametrize("n", SCAN_SHAPES)
 @pytest.mark.parametrize("layout", SCAN_LAYOUTS)
 def test_frame_scan_shapes(layout, n):
-    """The frame-state scan over wave edges, block edges and the second round of
-    the aggregate scan: 0-3 byte payloads, so code points straddle fragments and
-    the state matters across every edge."""
-    b, first, carry_in, expect, carry_want = scan_case(layout, n)
-    assert n < 64 or {ref.OK, ref.BAD, ref.AFTER_BAD, ref.NOT_TEXT} <= set(expect)
+    """The frame-state scan over wave edges, block edges and more than one wave of
+    aggregates (65,539 frames: 257 aggregates, still one round of the aggregate
+    scan; test_frame_scan_rounds goes past it): 0-3 byte payloads, so code points
+    straddle fragments and the state matters across every edge."""
+    check_scan_case(layout, scan_case(layout, n))
+
+
+def check_scan_case(layout, case):
+    b, first, carry_in, expect, carry_want = case
+    assert b.n < 64 or {ref.OK, ref.BAD, ref.AFTER_BAD, ref.NOT_TEXT} <= set(expect)
     one = layout == "one_stream"
     out, carry, st = run_gpu(b, masked=True, stream_first=None if one else first, carry_in=carry_in)
     assert st == 0
@@ -525,6 +562,168 @@ def test_frame_scan_shapes(layout, n):
     assert bad.size == 0, (bad[:10], out[bad[:10]], expect[bad[:10]])
     bad = np.nonzero((carry != carry_want).any(axis=1))[0]
     assert bad.size == 0, (bad[:10], carry[bad[:10]], carry_want[bad[:10]])
+
+
+# ---------------------------------------------------------------- frame-scan rounds
+
+# Past one round of the aggregate scan (SCAN_R aggregates of SCAN_B frames): the round edge itself, round two in
+# lanes 0 and 1, round two past a wave edge (an aggregate in lane 64: a lane takes four), round three.
+ROUND_EDGE = [SCAN_U - 1, SCAN_U, SCAN_U + 1]
+ROUND_TWO_LANE_1 = SCAN_U + 4 * SCAN_B + 1
+ROUND_TWO_LANE_64 = SCAN_U + 256 * SCAN_B + 1
+ROUND_THREE = 2 * SCAN_U + 3
+SCAN_ROUND_CASES = [(layout, ROUND_TWO_LANE_1) for layout in SCAN_LAYOUTS] + \
+    [(layout, n) for n in ROUND_EDGE + [ROUND_TWO_LANE_64, ROUND_THREE] for layout in ("one_stream", "block_edge_streams")]
+
+
+def scan_aggregates_of(n):
+    return -(-n // SCAN_B)
+
+
+def test_scan_round_shapes_have_the_aggregates_they_claim():
+    """CPU, from the header's constants."""
+    assert scan_aggregates_of(max(SCAN_SHAPES)) == SCAN_B + 1 <= SCAN_R  # one round: more than one wave of aggregates
+    assert [scan_aggregates_of(n) for n in ROUND_EDGE] == [SCAN_R, SCAN_R, SCAN_R + 1]
+    assert scan_aggregates_of(ROUND_TWO_LANE_1) == SCAN_R + 5       # round two: four in lane 0, one in lane 1
+    assert scan_aggregates_of(ROUND_TWO_LANE_64) == SCAN_R + 257    # round two: the last one in lane 256 / 4 = 64
+    assert scan_aggregates_of(ROUND_TWO_LANE_64 - SCAN_B) == SCAN_R + 256  # and no smaller count has one there
+    assert scan_aggregates_of(ROUND_THREE) == 2 * SCAN_R + 1 > 2 * SCAN_R
+    assert ROUND_TWO_LANE_64 == 327681 and SCAN_U == 262144  # the figures as typed in the design
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout,n", SCAN_ROUND_CASES)
+def test_frame_scan_rounds(layout, n):
+    """The second and third round of the aggregate scan: what round one composed
+    (scan_aggregates' run) stands in front of every later aggregate."""
+    check_scan_case(layout, scan_case.__wrapped__(layout, n))  # too large to keep
+
+
+# ---------------------------------------------------------------- state across the round edge
+
+def edge_fill():
+    """Ordinary content to cut prefixes and tails from."""
+    return fill_messages([k % 4 for k in range(2048)], 77)
+
+
+def round_edge_frames(head_block, piece_block, second, tail=300):
+    """One stream.  A text head without FIN whose payload ends in E2 in block
+    head_block; `second` (82 completes the code point so far, 61 breaks it) in a
+    CONTINUE in block piece_block, AC 21 in a CONTINUE|FIN in the block after it;
+    between them only PINGs with payloads >= 0x80 and empty CONTINUEs, so what the
+    head left has to travel through every block aggregate between.
+    -> (frames, dict of the head's, the second piece's and the FIN's index)."""
+    head, piece, fin = head_block * SCAN_B + 10, piece_block * SCAN_B + 20, (piece_block + 1) * SCAN_B + 30
+    unit = edge_fill()
+    frames = (unit * (head // len(unit) + 1))[:head]
+    frames.append((T_, b"x\xe2"))
+    pings = [(PING | FIN, bytes([0x80 + k, 0xBF - k])) for k in range(4)]
+    frames += [pings[(i >> 1) & 3] if i & 1 else (C_, b"") for i in range(head + 1, fin)]
+    frames[piece] = (C_, second)
+    frames.append((C_ | FIN, b"\xac\x21"))
+    frames += unit[:tail]
+    return frames, dict(head=head, piece=piece, fin=fin)
+
+
+OK_PIECE, BAD_PIECE = b"\x82", b"\x61"
+# (head's block, second piece's block): around the edge of round one and of round two.  The pieces' aggregates
+# lie in lane 1 of their round (a lane takes four), so the empty CONTINUEs of lane 0's four blocks and the pieces
+# both need what the rounds before composed; "wave": in lane 64, past a wave edge of that round's block scan.
+EDGE_ROUNDS = {2: (SCAN_R - 3, SCAN_R + 5), 3: (2 * SCAN_R - 3, 2 * SCAN_R + 5)}
+EDGE_CASES = {"round2": EDGE_ROUNDS[2], "round2_wave": (SCAN_R - 3, SCAN_R + 257), "round3": EDGE_ROUNDS[3]}
+# two calls: the head in the first, the cut inside the filler run, the pieces in lane 1 of the second call's round two
+TWO_CALL_BLOCKS, TWO_CALL_CUT = (1, SCAN_R + 7), 2 * SCAN_B + 17
+
+
+def round_edge_expect(frames, at, second):
+    """The reference's verdicts, and the typed claims on them."""
+    expect = want(frames)
+    between = range(at["head"] + 1, at["fin"])
+    empties = np.array([i for i in between if frames[i] == (C_, b"")])
+    pings = np.array([i for i in between if frames[i][0] == PING | FIN])
+    assert len(empties) + len(pings) + 1 == len(between) and (expect[pings] == ref.NOT_TEXT).all()
+    assert expect[at["head"]] == ref.OK and (expect[empties[empties < at["piece"]]] == ref.OK).all()
+    if second == OK_PIECE:
+        assert (expect[empties] == ref.OK).all() and expect[at["piece"]] == ref.OK and expect[at["fin"]] == ref.OK
+    else:
+        assert expect[at["piece"]] == ref.BAD and expect[at["fin"]] == ref.AFTER_BAD
+        assert (expect[empties[empties > at["piece"]]] == ref.AFTER_BAD).all()
+    return expect
+
+
+def round_edge_batch(frames, seed=3):
+    rng = np.random.default_rng(seed)
+    lens = np.array([len(p) for _, p in frames], dtype=np.int64)
+    gaps = rng.integers(2, 15, size=len(frames))
+    offs = np.cumsum(gaps + lens) - lens
+    return Batch(frames, offs, int(offs[-1] + lens[-1]) + 5, seed=seed)
+
+
+def test_round_edge_cases_straddle_the_rounds_they_claim():
+    """CPU, from the header's constants: the head's block lies below the round
+    edge and the FIN's above it with a whole filler block on either side, the
+    pieces' aggregates in the lane the case names, in the second call of the
+    two-call case too; and the reference's answers (round two)."""
+    for name, (hb, pb) in EDGE_CASES.items():
+        rnd = 3 if name == "round3" else 2
+        edge = (rnd - 1) * SCAN_R  # the first aggregate of the round
+        assert hb <= edge - 2 and edge + 1 <= pb  # blocks hb + 1 .. edge - 1 and edge .. pb - 1: whole, filler only
+        assert (pb - edge) // 4 == (pb + 1 - edge) // 4 == (64 if name == "round2_wave" else 1)  # the pieces' lane
+        if name == "round2":
+            frames, at = round_edge_frames(hb, pb, OK_PIECE)
+            assert at["head"] // SCAN_B == hb and at["piece"] // SCAN_B == pb and at["fin"] // SCAN_B == pb + 1
+            assert scan_aggregates_of(len(frames)) > edge + 2
+            for second in (OK_PIECE, BAD_PIECE):
+                fr, _ = round_edge_frames(hb, pb, second)
+                expect = round_edge_expect(fr, at, second)
+                # cut off before the FIN, the stream stays inside the message
+                left = scan_carry_after(fr[:at["fin"]], expect[:at["fin"]], bytes(8))
+                assert left == (bytes([3, 0x82, 0xE2, 0x78, 0, 0, 0, 0]) if second == OK_PIECE else
+                                bytes([7, 0x61, 0xE2, 0x78, 0, 0, 0, 0]))
+    hb, pb = TWO_CALL_BLOCKS
+    head, piece = hb * SCAN_B + 10, pb * SCAN_B + 20
+    assert head < TWO_CALL_CUT < piece and (piece - TWO_CALL_CUT) // SCAN_B == SCAN_R + 5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("second", [OK_PIECE, BAD_PIECE], ids=["ok", "bad"])
+@pytest.mark.parametrize("case", list(EDGE_CASES))
+def test_message_open_across_rounds(case, second):
+    """The analogue of the msg and proto files' test_message_open_across_blocks:
+    "open, checked, inside U+20AC" crosses the edge of round one (two) through
+    scan_aggregates' run, not through any block's own scan.  Whole, and cut off
+    before the FIN: the carry the stream leaves."""
+    frames, at = round_edge_frames(*EDGE_CASES[case], second)
+    expect = round_edge_expect(frames, at, second)
+    b = round_edge_batch(frames)
+    for hi in (b.n, at["fin"]):
+        out, carry, st = run_gpu(b, masked=case == "round2", hi=hi)
+        assert st == 0
+        bad = np.nonzero(out != expect[:hi])[0]
+        assert bad.size == 0, (hi, bad[:10], out[bad[:10]], expect[bad[:10]])
+        left = scan_carry_after(frames[:hi], expect[:hi], bytes(8))
+        assert bytes(carry[0]) == left, (hi, carry[0], left)
+        if hi == at["fin"]:
+            assert carry[0][0] == (3 if second == OK_PIECE else 7)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("second", [OK_PIECE, BAD_PIECE], ids=["ok", "bad"])
+def test_message_open_across_rounds_in_two_calls(second):
+    """The batch cut inside the filler run: in the second call the state comes in
+    as carry_in at frame 0 and reaches the pieces in round two through run."""
+    frames, at = round_edge_frames(*TWO_CALL_BLOCKS, second)
+    expect = round_edge_expect(frames, at, second)
+    b = round_edge_batch(frames)
+    c = TWO_CALL_CUT
+    out1, carry1, st1 = run_gpu(b, hi=c)
+    assert st1 == 0 and bytes(carry1[0]) == bytes([3, 0xE2, 0x78, 0, 0, 0, 0, 0])
+    out2, carry2, st2 = run_gpu(b, masked=True, carry_in=carry1, lo=c)
+    assert st2 == 0
+    got = np.concatenate([out1, out2])
+    bad = np.nonzero(got != expect)[0]
+    assert bad.size == 0, (bad[:10], got[bad[:10]], expect[bad[:10]])
+    assert bytes(carry2[0]) == scan_carry_after(frames, expect, bytes(8))
 
 
 # ---------------------------------------------------------------- contract
